@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the microfacet_tensorf2 hot path on MI355X (see BASELINE.json / SURVEY.md 8d).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--rays-per-gpu R] [--grid G] [--mode train|infer]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--rays-per-gpu R] [--grid G] [--mode train|infer] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 launches itself as N ranks under torch.distributed.run (one process per GPU, RCCL); when the
 driver has already done that (WORLD_SIZE set) the process is one of the ranks.
@@ -306,6 +306,69 @@ def cpu_baseline(budget_s=150.0, warm=1, timed=3):
 
 LINE_LIMIT = 6144           # bytes: the driver keeps an 8 KB tail of stdout and parses the last line out of it (round 5's 21 KB line was not parsed)
 DETAIL_FILE = "bench_detail.json"
+DUMP_LIMIT = 64 << 20       # bytes: what --dump-outputs writes in all
+
+
+class FixedStart:
+    """--dump-outputs: the state the last timed step starts from, the same in every run.  The training steps accumulate their
+    gradients with float atomics, and Adam turns rounding-level differences of the gradients into parameter differences of the
+    order of the learning rate within a few dozen steps: the model a late step starts from is not repeatable, its inputs are.
+    Taken before the first training step: the parameters as built (a copy); restore() writes them back in place (the derived
+    tables see the new versions and are rebuilt), zeroes Adam's moments (the step count, learning rate and schedule depend on
+    the number of steps only) and returns a fresh noise source with the run's seed."""
+
+    def __init__(self, trainer, make_noise):
+        self.trainer, self.make_noise = trainer, make_noise
+        self.params = [(p, p.detach().clone()) for p in trainer.nerf.parameters()]
+
+    def restore(self):
+        import torch
+        with torch.no_grad():
+            for p, v in self.params:
+                p.copy_(v)
+            for st in self.trainer.optimizer.state.values():
+                for k in ("exp_avg", "exp_avg_sq"):
+                    if k in st:
+                        st[k].zero_()
+        fast = self.trainer.fast
+        if fast is not None:
+            fast.prefetch()                     # the step's derived tables, as after an optimizer step
+        return self.make_noise()
+
+
+def step_outputs(last, nerf):
+    """what the last timed training step computed and handed back: its statistics (per-chunk loss, sample counts of the last chunk),
+    the parameter gradients it summed and the model it updated -> {name: numpy array}"""
+    import numpy as np
+    import torch
+    losses = last._losses
+    out = {"loss_per_chunk": (torch.stack(losses).double().cpu().numpy() if losses else np.zeros(0)),
+           "n_samples": np.asarray(last["n_samples"], dtype=np.float64)}
+    for name, p in nerf.named_parameters():
+        for kind, t in (("grad.", p.grad), ("param.", p.detach())):
+            if t is not None:
+                out[kind + name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs DIR: one DIR/<name>.npy per array (float64 stays float64, everything else float32), at most `limit` bytes in
+    all.  The budget is shared smallest array first; an array larger than its share is written as a fixed sample of its flattened
+    elements (seed 0, indices ascending), so two builds run with the same arguments are compared element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    budget, left = limit - 1024 * len(arrays), len(arrays)          # (1 KB per file for the .npy header)
+    for k in sorted(arrays, key=lambda k_: (arrays[k_].nbytes, k_)):
+        a = arrays[k]
+        share = budget // left
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        budget -= a.nbytes
+        left -= 1
 
 
 def _r(x, nd=4):
@@ -436,7 +499,9 @@ def flush_c_stdio():
         pass
 
 
-def time_train(trainer, batches, focal, noise, warmup, steps, chunk, sync, global_rays=None):
+def time_train(trainer, batches, focal, noise, warmup, steps, chunk, sync, global_rays=None, reset_last=None):
+    """`reset_last() -> noise`: called before the last timed step with the clock stopped; puts the trainer into a fixed state and
+    returns the noise source that step draws from (--dump-outputs: the last step's outputs then repeat from run to run)"""
     import torch  # noqa: F401
     nb = len(batches)
     for i in range(warmup):
@@ -447,6 +512,13 @@ def time_train(trainer, batches, focal, noise, warmup, steps, chunk, sync, globa
     cpu0 = time.process_time()
     rays_done, last, comm, first = 0, None, [], None
     for i in range(warmup, warmup + steps):
+        if reset_last is not None and i == warmup + steps - 1:
+            sync()
+            t_pause, cpu_pause = time.perf_counter(), time.process_time()
+            noise = reset_last()
+            sync()
+            t0 += time.perf_counter() - t_pause
+            cpu0 += time.process_time() - cpu_pause
         # (the loop knows its next batch, as train.py's permutation sampler does: the sampler of its first chunk is prefetched)
         last = trainer.step(*batches[i % nb], focal, noise=noise, update_controllers=False, fixed_chunk=chunk,
                             global_rays=global_rays)
@@ -526,7 +598,7 @@ def make_batches(nerf, n, rays_per_gpu, rank, device, distinct=48):
     return out, focal
 
 
-def time_infer(nerf, device, frames, warm_frames=1, chunk=None):
+def time_infer(nerf, device, frames, warm_frames=1, chunk=None, keep=None):
     """full FRAME x FRAME frames of the S1 camera, eval_batch_size rays per chunk, rendered to completion.  The warm-up is
     one whole frame: the chunks of a frame differ in their sample counts, and the first pass over them is the caching
     allocator growing its pools (tools/infer_host_profile.py: 333 ms for the first frame, 101 ms for every later one) --
@@ -555,6 +627,8 @@ def time_infer(nerf, device, frames, warm_frames=1, chunk=None):
     dt = time.perf_counter() - t0
     nerf.train(was_training)
     assert rgb.shape[0] == rays.shape[0]
+    if keep is not None:
+        keep["rgb"] = rgb              # the last timed frame
     return dt, rays.shape[0] * frames, chunk, cold
 
 
@@ -910,6 +984,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--contexts", type=int, default=None, help="chunk contexts of a multi-chunk step (default: NMF_CHUNK_CONTEXTS or 2; 1 = sequential)")
     ap.add_argument("--detail-dir", default=None, help=f"where {DETAIL_FILE} (the full result: per-kernel table, notes, every leg) is written; default: next to bench.py")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (train: per-chunk loss, sample counts, the "
+                         "parameter gradients and every parameter after the update; infer: the last frame's rgb) as DIR/<name>.npy, at "
+                         "most 64 MB in all.  The last training step then starts from a fixed state (the parameters as built, Adam's "
+                         "moments zero, the noise seed), restored with the clock stopped, so that its outputs repeat from run to run")
     ap.add_argument("--leg", default=None, help="internal: `host_paths` = the host-bound legs of `extras` in this (fresh) process, one JSON line")
     ap.add_argument("--core", action="append", default=[], metavar="ATTR=0|1",
                     help="A/B only: a switch of the C++ pass (csrc/step_core.inc: env_split, overlap ...) set before the warm-up; "
@@ -998,7 +1077,10 @@ def main():
                 f"800x800 camera")
 
     if args.mode == "infer":
-        dt, n_rays, chunk, _cold = time_infer(nerf, device, frames=max(args.steps, 1))
+        kept = {}
+        dt, n_rays, chunk, _cold = time_infer(nerf, device, frames=max(args.steps, 1), keep=kept)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"rgb": kept["rgb"].float().cpu().numpy()})
         tt = torch.tensor([dt, float(n_rays)], dtype=torch.float64, device=device)
         if world > 1:
             tmax = tt.clone()
@@ -1032,6 +1114,7 @@ def main():
         trainer.fast.set_switch(k, bool(int(v)))
     noise = DeviceNoise(device, seed=1000 + rank)
     batches, focal = make_batches(nerf, args.warmup + args.steps, args.rays_per_gpu, rank, device)
+    fixed = FixedStart(trainer, lambda: DeviceNoise(device, seed=1000 + rank)) if args.dump_outputs else None
     fx = hip_mod.HOST_EXT
     timed_calls = fx is not None and hasattr(fx, "kernel_timing_begin") and trainer.fast is not None and trainer.fast.core() is not None
     n_probe = min(args.warmup, 8) if timed_calls else 0
@@ -1057,9 +1140,12 @@ def main():
     timer.enabled = True
     if dominant:
         fx.kernel_timing_begin(dominant)            # inside the timed region: events around the launches of the dominant kernel only
-    dt, rays_done, last, comm_ms = time_train(trainer, batches, focal, noise, 0, args.steps, chunk_rays, sync)
+    dt, rays_done, last, comm_ms = time_train(trainer, batches, focal, noise, 0, args.steps, chunk_rays, sync,
+                                              reset_last=fixed.restore if fixed is not None else None)
     dom_live = fx.kernel_timing_end().get(dominant) if dominant else None
     timer.enabled = False
+    if args.dump_outputs and rank == 0:        # (before the instrumented steps below move the parameters on)
+        dump_outputs(args.dump_outputs, step_outputs(last, nerf))
 
     tt = torch.tensor([dt, float(rays_done), 1.0], dtype=torch.float64, device=device)
     if world > 1:

@@ -1,4 +1,4 @@
-"""Writes the two config fixtures (data only: hyper-parameter values).
+"""Writes the three config fixtures (data only: hyper-parameter values).
     python tests/golden/make_config_fixture.py
 
 config_resolved.json   what the reference's YAML files resolve to for `model=microfacet_tensorf2 field=tensorf_og dataset=lego`
@@ -9,6 +9,10 @@ hydra_config_car.json  /root/reference/config.yaml -- a resolved config written 
                        to the command-line overrides that reproduce it from today's YAML files (the field file has changed since:
                        grid 64 -> 128, density_shift -10 -> -4, `numer_grad` dropped, ...).  This is the pin of the composer that
                        the composer did not produce: tests/test_config.py composes those overrides and compares every leaf.
+config_scenes.json     what the reference's YAML files resolve to for every other built-in scene (nmf_amd/config.py DATASETS) with
+                       `model=microfacet_tensorf2 field=tensorf_og`: the `dataset` group of each (every other key equals
+                       config_resolved.json, checked here), and the composition of hydra_config_car.json's overrides -- so that
+                       tests/test_config.py compares the built-in tree against the reference's files without a reference checkout.
 """
 import importlib.util
 import json
@@ -37,3 +41,16 @@ with open(os.path.join(HERE, "hydra_config_car.json"), "w") as f:
     json.dump({"source": "/root/reference/config.yaml (OmegaConf.save of a hydra-composed run)", "overrides": overrides,
                "run_time_leaves": run_time, "config": hydra}, f, indent=1, sort_keys=True)
 print("wrote hydra_config_car.json")
+
+from nmf_amd.config import DATASETS  # noqa: E402
+
+scenes = {}
+for name in DATASETS:
+    if name == "s2_orbit":                     # (this package's offline stand-in: no file of the reference)
+        continue
+    c = yc.compose("/root/reference/configs", [f"dataset={name}", "model=microfacet_tensorf2", "field=tensorf_og"])
+    assert {k: v for k, v in c.items() if k != "dataset"} == {k: v for k, v in cfg.items() if k != "dataset"}, name
+    scenes[name] = c["dataset"]
+with open(os.path.join(HERE, "config_scenes.json"), "w") as f:
+    json.dump({"dataset": scenes, "hydra_car_composed": yc.compose("/root/reference/configs", overrides)}, f, indent=1, sort_keys=True)
+print("wrote config_scenes.json:", len(scenes), "scenes")

@@ -47,3 +47,28 @@ def test_bench_line_never_exceeds_the_limit_even_with_bloated_legs():
     assert len(text) < 6144
     rec = json.loads(text)
     assert "roofline" in rec and "cpu_baseline" in rec and len(rec["config"]["workload"]) <= 300
+
+
+def test_dump_outputs_keeps_dtypes_and_the_size_limit(tmp_path):
+    """--dump-outputs: float64 stays float64, the rest is written as float32, small arrays whole; arrays beyond their share of
+    the limit are a fixed sample, the same on every call, and the files together stay within the limit"""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"loss": np.array([1.5, 2.5]), "n": np.array([3, 4], dtype=np.int64), "half": rng.random(10).astype(np.float16),
+              "big": rng.random((64, 1000)).astype(np.float32), "bigger": rng.random(200000)}
+    limit = 256 << 10
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["loss"].dtype == np.float64 and np.array_equal(got["loss"], arrays["loss"])
+    assert got["n"].dtype == np.float32 and np.array_equal(got["n"], [3, 4])
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], arrays["half"].astype(np.float32))
+    assert got["bigger"].dtype == np.float64 and 0 < got["bigger"].size < arrays["bigger"].size
+    assert got["big"].dtype == np.float32 and 0 < got["big"].size < arrays["big"].size
+    assert np.isin(got["bigger"], arrays["bigger"]).all() and np.isin(got["big"], arrays["big"]).all()
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

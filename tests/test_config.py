@@ -1,6 +1,6 @@
 """Config surface: the hand-resolved dictionaries of nmf_amd/config.py and the YAML composer nmf_amd/yaml_config.py against
-the values the reference's own YAML files resolve to (tests/golden/config_resolved.json, written by
-tests/golden/make_config_fixture.py from /root/reference/configs)."""
+the values the reference's own YAML files resolve to (tests/golden/config_resolved.json, config_scenes.json and
+hydra_config_car.json, written by tests/golden/make_config_fixture.py from the reference's configs/ directory)."""
 import importlib.util
 import json
 import os
@@ -75,10 +75,16 @@ def test_yaml_composer_semantics(tmp_path):
     assert yc._load(str(out))["model"]["params"]["eps"] == 2.5e-4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference checkout not present")
-def test_composer_on_the_reference_tree():
+def test_composer_on_the_reference_tree(tmp_path):
+    """a configs/ directory with the reference's layout (default.yaml, model/, field/, dataset/), written as YAML files from the
+    built-in tree, composes through the file reader to what the reference's own files resolve to (config_resolved.json)"""
+    sys_path_root()
+    from nmf_amd.config import builtin_tree
     yc = _yc()
-    cfg = yc.compose("/root/reference/configs", ["model=microfacet_tensorf2", "field=tensorf_og", "dataset=lego"])
+    for rel, node in builtin_tree().items():
+        (tmp_path / "configs" / rel).parent.mkdir(parents=True, exist_ok=True)
+        yc.dump(node, str(tmp_path / "configs" / (rel + ".yaml")))
+    cfg = yc.compose(str(tmp_path / "configs"), ["model=microfacet_tensorf2", "field=tensorf_og", "dataset=lego"])
     assert cfg == json.load(open(GOLD))
     assert cfg["dataset"]["near_far"] == [2.5, 7] and cfg["model"]["arch"]["rf"]["_target_"] == "fields.tensoRF.TensorVMSplit"
 
@@ -99,20 +105,20 @@ def _compare(mine, ref, skip=()):
 
 
 HYDRA = os.path.join(ROOT, "tests", "golden", "hydra_config_car.json")
+SCENES = os.path.join(ROOT, "tests", "golden", "config_scenes.json")      # the reference's files, composed (make_config_fixture.py)
 
 
 def test_composer_reproduces_a_config_hydra_itself_wrote():
-    """The pin the composer did not produce: /root/reference/config.yaml was written by hydra / OmegaConf (train.py:485) for a
+    """The pin the composer did not produce: the reference's config.yaml was written by hydra / OmegaConf (train.py:485) for a
     dataset=car model=microfacet_tensorf2 field=tensorf_og run.  Composing the same choices + the overrides that undo what the YAML
     files have changed since gives the same key set and every leaf (the three biases the run calibrated are written at run time).
-    Runs from the built-in tree (no reference checkout needed) and, where the checkout exists, from the reference's own files."""
+    Runs from the built-in tree, and checks what the reference's own files compose to (config_scenes.json) the same way."""
     sys_path_root()
     from nmf_amd import yaml_config as yc
     fx = json.load(open(HYDRA))
     n = _compare(yc.compose(None, fx["overrides"]), fx["config"], skip=fx["run_time_leaves"])
     assert n > 150
-    if os.path.isdir("/root/reference/configs"):
-        _compare(yc.compose("/root/reference/configs", fx["overrides"]), fx["config"], skip=fx["run_time_leaves"])
+    _compare(json.load(open(SCENES))["hydra_car_composed"], fx["config"], skip=fx["run_time_leaves"])
 
 
 def sys_path_root():
@@ -123,7 +129,7 @@ def sys_path_root():
 
 def test_builtin_tree_composes_what_the_reference_files_compose():
     """`python -m nmf_amd.train dataset=lego ...` without a configs/ directory: the built-in tree (nmf_amd/config.py) resolves to the
-    fixture of the reference's files for lego, and for every built-in scene to what the reference's files give here."""
+    fixture of the reference's files for lego, and for every built-in scene to what the reference's files give (config_scenes.json)."""
     sys_path_root()
     from nmf_amd import yaml_config as yc
     from nmf_amd.config import DATASETS
@@ -131,12 +137,11 @@ def test_builtin_tree_composes_what_the_reference_files_compose():
     assert yc.compose(None, ["dataset=lego", "model=microfacet_tensorf2", "field=tensorf_og"]) == json.load(open(GOLD))
     with pytest.raises(FileNotFoundError):
         yc.compose(None, ["model=brdf_tcnn"])                    # outside the path: named, not silently replaced
-    if os.path.isdir("/root/reference/configs"):
-        for name in DATASETS:
-            if name == "s2_orbit":
-                continue
-            ov = [f"dataset={name}", "model=microfacet_tensorf2", "field=tensorf_og"]
-            assert yc.compose(None, ov) == yc.compose("/root/reference/configs", ov), name
+    scenes = json.load(open(SCENES))["dataset"]
+    assert sorted(scenes) == sorted(name for name in DATASETS if name != "s2_orbit")
+    for name in scenes:
+        ov = [f"dataset={name}", "model=microfacet_tensorf2", "field=tensorf_og"]
+        assert yc.compose(None, ov) == dict(json.load(open(GOLD)), dataset=scenes[name]), name
 
 
 def test_train_cli_composes_hydra_tokens_and_flags():

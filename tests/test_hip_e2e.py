@@ -527,6 +527,50 @@ def test_bench_json_is_the_last_stdout_line_with_rccl():
     assert rec["config"]["backend"] == "nccl" and rec["config"]["comm_bytes_per_step"] > 10e6
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: the per-chunk loss and sample counts of the last timed step, the parameter gradients it summed
+    and every parameter of the model it updated, one .npy each (float32 / float64), finite, within 64 MB; the line still reports
+    `steps` and `ms_per_step`.  Two runs with the same arguments write the same outputs up to the rounding of the float atomics."""
+    import json as _json
+    import subprocess
+    import sys
+    from nmf_amd.config import build_model
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NMF_BENCH_SHARE_GPU", "NMF_BENCH_BACKEND"):
+        env.pop(k, None)
+    nerf, _ = build_model(grid=128, bg_resolution=512, device="cpu")
+    names = [n for n, _ in nerf.named_parameters()]
+    runs = []
+    for d in ("a", "b"):
+        out = tmp_path / d
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--no-cpu-baseline", "--no-extras", "--detail-dir", str(tmp_path), "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _json.loads(r.stdout.rstrip().splitlines()[-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        files = sorted(os.listdir(out))
+        assert {"loss_per_chunk.npy", "n_samples.npy"} | {f"param.{n}.npy" for n in names} <= set(files)
+        assert set(files) <= {"loss_per_chunk.npy", "n_samples.npy"} | {f"{k}.{n}.npy" for n in names for k in ("param", "grad")}
+        assert {f"grad.rf.{f}.app_plane.0.npy" for f in ("density_rf", "app_rf")} | {"grad.bg_module.bg_mat.npy"} <= set(files)
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        got = {f[:-4]: np.load(out / f) for f in files}
+        for k, a in got.items():
+            assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
+        assert got["loss_per_chunk"].shape == (rec["config"]["chunks_per_step"],)
+        assert got["n_samples"].tolist() == [float(v) for v in rec["config"]["samples_per_chunk"]]
+        assert got["param.bg_module.bg_mat"].shape == (1, 3, 512, 1024)
+        runs.append(got)
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    assert np.array_equal(a["n_samples"], b["n_samples"])
+    for k in sorted(a):
+        x, y = a[k].astype(np.float64), b[k].astype(np.float64)
+        scale = max(float(np.abs(y).max()), 1e-30)
+        assert np.abs(x - y).max() <= 1e-5 * scale, (k, float(np.abs(x - y).max()), scale)
+
+
 def test_edge_cases_all_rays_miss_and_single_ray():
     """Rays that never enter the AABB / hit only empty space give M = 0 at level 0; a single ray batch works."""
     from nmf_amd.config import build_model
