@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 116
+#define NMF_ABI_VERSION 117
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -673,6 +673,31 @@ typedef struct {
     int32_t dst_is_f64;      /* 0: fp32, 1: fp64, 2: bfloat16 (fp32 source only, round to nearest even) */
 } nmf_copy_slot;
 int nmf_multi_copy(const nmf_copy_slot* slots, int32_t n_slots, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Evaluation metrics of renderer.py:195-560 (evaluate).  Not on the training path; deterministic (fp64 partial sums per
+ * workgroup in the workspace, summed per view in a fixed order by a second launch: no float atomics), so a view's value is
+ * bit-identical from run to run and independent of how many views share a call.  n_img == 0 is a no-op.
+ *
+ * nmf_ssim: utils.py:90-136 (rgb_ssim) for filter_size 11.  a, b: contiguous [n_img][H][W][C] fp32, C == 3, H, W >= 11.
+ * taps11: HOST array of the 11 normalised Gaussian taps (fp64, utils.py:101-106), read at call time.  c1 = (k1 max_val)^2,
+ * c2 = (k2 max_val)^2.  Moments and the per-pixel formula in fp64 (valid-mode separable filter, sigma00 / sigma11 clamped at
+ * 0, sigma01 limited to sign * min(sqrt(sigma00 sigma11), |sigma01|)).  mean_out [n_img] fp64: the mean of the map over pixels
+ * and channels; map_out [n_img][H-10][W-10][C] fp32 or NULL.  workspace >= nmf_ssim_workspace_bytes(n_img, H, W, C).
+ * ---------------------------------------------------------------------------------------- */
+int nmf_ssim(const float* a, const float* b, int64_t n_img, int32_t H, int32_t W, int32_t C,
+             const double* taps11, double c1, double c2,
+             double* mean_out, float* map_out, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t nmf_ssim_workspace_bytes(int64_t n_img, int32_t H, int32_t W, int32_t C);
+/* nmf_normal_err: renderer.py:369-389 per view.  pred, gt: [n_img][n_px][3] fp32 normals, acc: [n_img][n_px] fp32 alpha.
+ * Per pixel in fp32 in the torch expression's order: q = (n*127 + 128) truncated toward zero, (q - 128) / 127, divided by
+ * sqrt(sum n^2 + 1e-6), dot clipped to [1e-8, 1] (1 - 1e-8 is 1 in fp32), acos * 180 / pi, NaN (or a non-finite normal) -> 0,
+ * times acc.  mean_out [n_img] fp64 = sum(err * acc) / sum(acc) (NaN when sum(acc) == 0, as the reference); err_map
+ * [n_img][n_px] fp32 (err * acc, what the reference writes to normal_err/) or NULL.
+ * workspace >= nmf_normal_err_workspace_bytes(n_img, n_px). */
+int nmf_normal_err(const float* pred, const float* gt, const float* acc, int64_t n_img, int64_t n_px,
+                   double* mean_out, float* err_map, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t nmf_normal_err_workspace_bytes(int64_t n_img, int64_t n_px);
 
 #ifdef __cplusplus
 }

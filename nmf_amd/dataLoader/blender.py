@@ -6,7 +6,8 @@ frames; produces the tensors train.py / renderer.py consume:
     img_wh, near_far, scene_bbox (+-1.5 * aabb_scale), white_bg, poses [N,4,4], fx / fy, intrinsics
 
 Pixel centres at +0.5, camera looks down +z after the blender->opencv flip (:45-47), directions unit-normalised (:120-122),
-fx = 0.5 w / tan(camera_angle_x / 2) (:97-104).  EXR frames / normal maps / depth are outside the microfacet_tensorf2 path.
+fx = 0.5 w / tan(camera_angle_x / 2) (:97-104).  Ground-truth normal maps `{file_path}_normal{normal_ext}` are read per view
+for evaluation (get_normal, :236-247); training on them (stack_norms), EXR frames and depth are outside the microfacet_tensorf2 path.
 """
 import json
 import os
@@ -68,6 +69,7 @@ class BlenderDataset(torch.utils.data.Dataset):
         ext = meta.get("ext", ".png")
         if "exr" in ext:
             raise NotImplementedError("EXR frames need an OpenEXR reader (not on the microfacet_tensorf2 benchmark path)")
+        normal_ext = meta.get("normal_ext", ext)
         self.near_far = meta.get("near_far", [2.0, 6.0])
         self.white_bg = meta.get("white_bg", self.white_bg)
         meta.setdefault("w", 800)
@@ -84,7 +86,7 @@ class BlenderDataset(torch.utils.data.Dataset):
         directions = get_ray_directions(h, w, [self.fx, self.fy])
         self.directions = directions / torch.norm(directions, dim=-1, keepdim=True)
         self.intrinsics = torch.tensor([[self.fx, 0, w / 2], [0, self.fy, h / 2], [0, 0, 1]]).float()
-        self.image_paths, self.poses, self.all_rays, self.all_rgbs, self.acc_maps = [], [], [], [], []
+        self.image_paths, self.normal_paths, self.poses, self.all_rays, self.all_rgbs, self.acc_maps = [], [], [], [], [], []
         frames = meta["frames"]
         interval = 1 if self.N_vis < 0 else max(len(frames) // self.N_vis, 1)
         for i in range(0, len(frames), interval):
@@ -94,6 +96,7 @@ class BlenderDataset(torch.utils.data.Dataset):
             self.poses.append(c2w)
             path = os.path.join(self.root_dir, f"{frame['file_path']}{ext}")
             self.image_paths.append(path)
+            self.normal_paths.append(os.path.join(self.root_dir, f"{frame['file_path']}_normal{normal_ext}"))
             img = _read_image(path, self.img_wh if self.downsample != 1.0 else None)          # [h, w, c]
             if img.shape[-1] == 4:
                 self.acc_maps.append(img[..., -1])
@@ -114,6 +117,22 @@ class BlenderDataset(torch.utils.data.Dataset):
 
     def world2ndc(self, points, lindisp=None):
         return (points - self.center.to(points.device)) / self.radius.to(points.device)
+
+    def has_normal(self, idx):
+        """True when view `idx` has a ground-truth normal map on disk"""
+        return os.path.exists(self.normal_paths[idx])
+
+    def get_normal(self, idx):
+        """blender.py:236-247: the first three channels; 8-bit maps (max > 2) are (x - 128) / 127, unit-normalised with the
+        fp32 eps as the lower clip; maps already in [0, 1] are (x - 0.5) * 2 -> [h, w, 3] float32"""
+        from PIL import Image
+        norms = torch.from_numpy(np.array(Image.open(self.normal_paths[idx])))[..., :3].float()
+        if norms.max() > 2:
+            norms = (norms - 128) / 127
+            norms = norms / torch.linalg.norm(norms, dim=-1, keepdim=True).clip(min=torch.finfo(torch.float32).eps)
+        else:
+            norms = (norms - 0.5) * 2
+        return norms
 
     def __len__(self):
         return len(self.all_rgbs)

@@ -73,6 +73,7 @@ EXPORTS = [
     "nmf_ray_compose_fwd", "nmf_ray_compose_bwd", "nmf_l1_mean_fwd", "nmf_l1_mean_bwd", "nmf_sqerr_fwd", "nmf_sqerr_bwd",
     "nmf_loss_mix_fwd", "nmf_loss_mix_bwd", "nmf_loss_head", "nmf_loss_head_workspace_bytes", "nmf_bg_adjoint", "nmf_vm_query_bwd_segments", "nmf_vm_query_bwd_segments_clean", "nmf_vm_bwd_clean_bytes", "nmf_vm_unpack_density_grad_l1", "nmf_vm_bin_plan", "nmf_vm_bin_plan_bytes", "nmf_vm_walk_workspace_bytes", "nmf_vm_query_bwd_planned", "nmf_sh_project",
     "nmf_retrace_scores", "nmf_argsort_f32", "nmf_argsort_workspace_bytes", "nmf_topk_select", "nmf_topk_select_workspace_bytes", "nmf_alpha_coarse", "nmf_alpha_coarse_words", "nmf_bounce_index_select", "nmf_bounce_prep_fwd_heads", "nmf_bounce_prep_heads_bwd", "nmf_multi_copy",
+    "nmf_ssim", "nmf_ssim_workspace_bytes", "nmf_normal_err", "nmf_normal_err_workspace_bytes",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -124,6 +125,8 @@ _lib.nmf_argsort_workspace_bytes.restype = C.c_int64
 _lib.nmf_topk_select_workspace_bytes.restype = C.c_int64
 _lib.nmf_alpha_coarse_words.restype = C.c_int64
 _lib.nmf_sat_lookup_bwd_workspace_bytes.restype = C.c_int64
+_lib.nmf_ssim_workspace_bytes.restype = C.c_int64
+_lib.nmf_normal_err_workspace_bytes.restype = C.c_int64
 
 
 def version():
@@ -1232,6 +1235,58 @@ def topk_select(keys, k):
 def multi_copy(slots, n):
     """slots: (CopySlot * k) host array; copies the first n (src -> dst, with fp32 <-> fp64 conversion) in one launch"""
     _check(_lib.nmf_multi_copy(slots, n, _stream()), "nmf_multi_copy")
+
+
+# ---- evaluation metrics (renderer.py:195-560) -----------------------------------------------------------------------
+def ssim_taps(filter_size=11, filter_sigma=1.5):
+    """the normalised 1-D Gaussian of utils.py:101-106, float64"""
+    hw = filter_size // 2
+    shift = (2 * hw - filter_size + 1) / 2
+    f_i = ((np.arange(filter_size) - hw + shift) / filter_sigma) ** 2
+    filt = np.exp(-0.5 * f_i)
+    return filt / np.sum(filt)
+
+
+def _batched(t, tail):
+    t = t.reshape(-1, *t.shape[-tail:]) if t.dim() > tail else t.unsqueeze(0)
+    return t.contiguous()
+
+
+def ssim(a, b, max_val=1.0, k1=0.01, k2=0.03, return_map=False, filter_sigma=1.5):
+    """SSIM of utils.py:90-136 (filter_size 11) over a batch: a, b fp32 device tensors [H,W,3] or [n,H,W,3] ->
+    float64 [n] (the mean of each view's map), and with return_map the fp32 map [n,H-10,W-10,3].  One launch for every
+    view; fp64 moments; bit-identical per view whatever else is in the batch."""
+    if a.shape != b.shape or a.dim() not in (3, 4):
+        raise NmfHipError(f"ssim: images must have equal shapes [H,W,3] or [n,H,W,3], got {tuple(a.shape)} / {tuple(b.shape)}")
+    A, B = _batched(a, 3), _batched(b, 3)
+    n, H, W, Cn = A.shape
+    taps = (C.c_double * 11)(*ssim_taps(11, filter_sigma))
+    mean = torch.empty(n, dtype=torch.float64, device=A.device)
+    smap = torch.empty((n, max(H - 10, 0), max(W - 10, 0), Cn), dtype=torch.float32, device=A.device) if return_map else None
+    nbytes = int(_lib.nmf_ssim_workspace_bytes(C.c_int64(n), C.c_int32(H), C.c_int32(W), C.c_int32(Cn)))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=A.device)
+    _check(_lib.nmf_ssim(_p(A, torch.float32), _p(B, torch.float32), C.c_int64(n), C.c_int32(H), C.c_int32(W), C.c_int32(Cn),
+                         C.addressof(taps), C.c_double((k1 * max_val) ** 2), C.c_double((k2 * max_val) ** 2), _p(mean),
+                         _p(smap), _p(ws), C.c_int64(ws.numel()), _stream()), "nmf_ssim")
+    return (mean, smap) if return_map else mean
+
+
+def normal_err(pred, gt, acc, return_map=False):
+    """per-view normal error of renderer.py:369-389: pred, gt fp32 device normals [n, P, 3] with the views' alpha acc [n, P]
+    (or one view: [P, 3] / [P]) -> float64 [n] = sum(err * acc) / sum(acc) in degrees (NaN when sum(acc) == 0), and with
+    return_map the fp32 err * acc in acc's shape."""
+    if pred.shape != gt.shape or pred.dim() not in (2, 3) or pred.shape[-1] != 3 or pred.shape[:-1] != acc.shape:
+        raise NmfHipError(f"normal_err: shapes {tuple(pred.shape)} / {tuple(gt.shape)} / {tuple(acc.shape)}")
+    n = pred.shape[0] if pred.dim() == 3 else 1
+    P, G, Acc = pred.reshape(n, -1, 3).contiguous(), gt.reshape(n, -1, 3).contiguous(), acc.reshape(n, -1).contiguous()
+    n_px = P.shape[1]
+    out = torch.empty(n, dtype=torch.float64, device=P.device)
+    emap = torch.empty_like(Acc) if return_map else None
+    nbytes = int(_lib.nmf_normal_err_workspace_bytes(C.c_int64(n), C.c_int64(n_px)))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=P.device)
+    _check(_lib.nmf_normal_err(_p(P, torch.float32), _p(G, torch.float32), _p(Acc, torch.float32), C.c_int64(n),
+                               C.c_int64(n_px), _p(out), _p(emap), _p(ws), C.c_int64(ws.numel()), _stream()), "nmf_normal_err")
+    return (out, emap.reshape(acc.shape)) if return_map else out
 
 
 # ---- host-side fast path ---------------------------------------------------------------------------------------------

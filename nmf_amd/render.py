@@ -7,6 +7,11 @@ renderer.py:56-106 `chunk_renderer`, :399-401 PSNR) for checkpoints written by T
 --fixed-bg swaps the learned environment map for another IntegralEquirect state_dict (relighting, train.py:96-138); the
 module is rebuilt at the resolution stored in that file (the reference hard-codes 512 and fails on other sizes).
 Prints one JSON line: frames, rays/s (render to completion, eval_batch_size rays per chunk), mean PSNR when ground truth exists.
+
+    python -m nmf_amd.render --ckpt log/lego.th --datadir /data/nerf_synthetic/lego --eval-dir log/lego/imgs_test_all
+
+--eval-dir (the reference's render_only + render_test, train.py:167-180) then evaluates the views with renderer.evaluation:
+frames, mean.txt and stats.yaml go to DIR, and the line gains ssim, norm_err and the evaluation's render / metric seconds.
 """
 import argparse
 import json
@@ -57,7 +62,11 @@ def main(argv=None):
     ap.add_argument("--res", type=int, default=800)
     ap.add_argument("--n-vis", type=int, default=-1)
     ap.add_argument("--chunk", type=int, default=None, help="rays per chunk (default: the model's eval_batch_size)")
+    ap.add_argument("--eval-dir", default=None,
+                    help="with --datadir: evaluate the test views (PSNR, SSIM, normal error) into this directory")
     args = ap.parse_args(argv)
+    if args.eval_dir and not args.datadir:
+        ap.error("--eval-dir needs --datadir (ground truth of a Blender scene)")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
     gt = None
@@ -88,6 +97,15 @@ def main(argv=None):
         for i in range(rgb.shape[0]):
             a = (rgb[i].clip(0, 1).reshape(wh[1], wh[0], 3) * 255).byte().cpu().numpy()
             Image.fromarray(a).save(os.path.join(args.out, f"{i:03d}.png"))
+    if args.eval_dir:
+        from .renderer import evaluation
+        from .train import test_all_record
+        t0 = time.perf_counter()
+        res = evaluation(ds, nerf, None, None, args.eval_dir, N_vis=-1, device=dev, noise=noise)
+        rec_all = test_all_record(res)
+        rec.update(ssim=rec_all["ssim"], norm_err=rec_all["norm_err"],
+                   eval_seconds=dict(total=round(time.perf_counter() - t0, 4), render=round(res["seconds"]["render"], 4),
+                                     metrics=round(res["seconds"]["metrics"], 4)))
     print(json.dumps(rec), flush=True)
     return rec
 

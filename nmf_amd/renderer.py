@@ -1,7 +1,11 @@
 """Chunked rendering -- counterpart of the reference's renderer.py: `chunk_renderer` (:56-106, the callable train.py:541
-and BundleRender use) and the evaluation PSNR (:399-401, :511-513)."""
+and BundleRender use), the evaluation PSNR (:399-401, :511-513) and the test-set evaluation `evaluation` / `evaluate`
+(:195-560: PSNR, SSIM and normal error per view, frames and mean.txt / stats.yaml)."""
+import os
+import time
 from collections import defaultdict
 
+import numpy as np
 import torch
 
 
@@ -100,3 +104,106 @@ def _eval_pass(nerf):
         else:
             object.__setattr__(nerf, "_fused_pass", fp)
     return fp if fp.supported() else None
+
+
+def _png(path, arr):
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(arr)).save(path)
+
+
+@torch.no_grad()
+def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", N_samples=-1, white_bg=False, ndc_ray=False,
+             compute_extra_metrics=True, device="cuda", noise=None, **kw):
+    """renderer.py:195-510 for the outputs the fused eval pass produces.  Per view of `iterator()` ((idx, im_idx, rays,
+    gt_rgb [H,W,3] or None)): PSNR of the 8-bit prediction (psnr_8bit), with compute_extra_metrics its SSIM against the
+    unclipped ground truth (renderer.py:403-404, nmf_ssim), and the normal error (renderer.py:357-390, nmf_normal_err) when
+    the data set has a normal map for the view.  Writes {prtx}{idx:03d}.png, world_normal/, acc_map/ and err/ PNGs with the
+    reference's 8-bit conversions, {prtx}mean.txt ([psnr, ssim, nan, nan]: LPIPS is not computed; [psnr] without extra
+    metrics) and stats{prtx}.yaml (psnr, ssim, norm_err).  LPIPS, videos, EXR outputs and the debug maps are not produced.
+    `renderer`, `N_samples` and `white_bg` are accepted for the reference's call shape (the model's own background and
+    sample budget are used).  -> dict(psnrs, norm_errs, ssims, seconds=dict(render, metrics))."""
+    from . import hip
+    if ndc_ray:
+        raise NotImplementedError("evaluation: ndc rays are not used by model=microfacet_tensorf2")
+    W, H = test_dataset.img_wh
+    focal = float(test_dataset.fx)
+    if savePath is not None:
+        for sub in ("", "world_normal", "acc_map", "err"):
+            os.makedirs(os.path.join(savePath, sub), exist_ok=True)
+    has_normal = getattr(test_dataset, "has_normal", None)
+    acc_maps = getattr(test_dataset, "acc_maps", [])
+    psnrs, ssims, norm_errs = [], [], []
+    t_render = t_metric = 0.0
+    was_training = tensorf.training
+    tensorf.eval()
+    for idx, im_idx, rays, gt_rgb in iterator():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ims = render_images(tensorf, rays.to(device), focal, noise=noise, keys=("rgb_map", "acc_map", "world_normal"))
+        rgb = ims["rgb_map"].reshape(H, W, 3)
+        acc = ims["acc_map"].reshape(H, W)
+        wn = ims["world_normal"].reshape(H, W, 3)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        t_render += t1 - t0
+        if gt_rgb is not None:
+            gt = gt_rgb.reshape(H, W, 3).to(rgb.device, torch.float32)
+            if has_normal is not None and im_idx < len(acc_maps) and has_normal(im_idx):
+                gt_n = test_dataset.get_normal(im_idx).to(rgb.device, torch.float32).reshape(1, -1, 3)
+                alpha = acc_maps[im_idx].reshape(1, -1).to(rgb.device, torch.float32)
+                norm_errs.append(float(hip.normal_err(wn.reshape(1, -1, 3).contiguous(), gt_n.contiguous(), alpha)[0]))
+            psnrs.append(float(psnr_8bit(rgb, gt)))
+            if compute_extra_metrics:
+                # renderer.py:399, the 8-bit prediction: k / 255 correctly rounded (the reference divides on the host; a device
+                # division by a scalar multiplies by the reciprocal, an ulp away for some k)
+                q = (torch.floor(rgb.clip(0, 1) * 255).double() / 255).float()
+                ssims.append(float(hip.ssim(q.contiguous(), gt.contiguous(), max_val=1.0)[0]))
+        t_metric += time.perf_counter() - t1
+        if savePath is not None:
+            # renderer.py:343-347, 414-415, 440-451, 489-492: 8-bit conversions of the reference
+            _png(os.path.join(savePath, f"{prtx}{idx:03d}.png"), (rgb.clamp(0, 1).cpu().numpy() * 255).astype("uint8"))
+            _png(os.path.join(savePath, "world_normal", f"{prtx}{idx:03d}.png"),
+                 (wn * 127 + 128).clamp(0, 255).byte().cpu().numpy())
+            _png(os.path.join(savePath, "acc_map", f"{prtx}{idx:03d}.png"),
+                 (255 * acc.clamp(0, 1).cpu().numpy()).astype(np.uint8))
+            if gt_rgb is not None:
+                err = (rgb.clip(0, 1) - gt.clip(0, 1)) + 0.5
+                _png(os.path.join(savePath, "err", f"{prtx}{idx:03d}.png"), (err.clamp(0, 1).cpu().numpy() * 255).astype("uint8"))
+    tensorf.train(was_training)
+
+    final_stats = {}
+    if psnrs:
+        psnr = float(np.mean(np.asarray(psnrs)))
+        final_stats["psnr"] = psnr
+        final_stats["norm_err"] = float(np.mean(np.asarray(norm_errs))) if norm_errs else 0
+        if compute_extra_metrics:
+            final_stats["ssim"] = float(np.mean(np.asarray(ssims)))
+            row = [psnr, final_stats["ssim"], np.nan, np.nan]                   # LPIPS alex / vgg: not computed
+        else:
+            row = [psnr]
+        if savePath is not None:
+            np.savetxt(os.path.join(savePath, f"{prtx}mean.txt"), np.asarray(row))
+    if savePath is not None:
+        import yaml
+        with open(os.path.join(savePath, f"stats{prtx}.yaml"), "w") as f:
+            yaml.dump(final_stats, f)
+    return dict(psnrs=psnrs, norm_errs=norm_errs, ssims=ssims, seconds=dict(render=t_render, metrics=t_metric))
+
+
+@torch.no_grad()
+def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=5, prtx="", N_samples=-1, white_bg=False,
+               ndc_ray=False, compute_extra_metrics=True, device="cuda", noise=None, **kw):
+    """renderer.py:513-560: every max(N // N_vis, 1)-th view of a stacked test set (all views with N_vis < 0) through
+    `evaluate`; the call shape of train.py:863-875."""
+    n = test_dataset.all_rays.shape[0]
+    step = 1 if N_vis < 0 else max(n // N_vis, 1)
+    idxs = list(range(0, n, step))
+    have_gt = len(test_dataset.all_rgbs) > 0
+
+    def iterator():
+        for idx, im_idx in enumerate(idxs):
+            rays = test_dataset.all_rays[im_idx].reshape(-1, test_dataset.all_rays.shape[-1])
+            yield idx, im_idx, rays, (test_dataset.all_rgbs[im_idx] if have_gt else None)
+
+    return evaluate(iterator, test_dataset, tensorf, renderer, savePath, prtx=prtx, N_samples=N_samples, white_bg=white_bg,
+                    ndc_ray=ndc_ray, compute_extra_metrics=compute_extra_metrics, device=device, noise=noise, **kw)

@@ -22,7 +22,9 @@ RGBA frames blended onto the white background as train.py:525-530 does); --save 
 TensorNeRF.load.
 
 Prints one JSON line per evaluation: iteration, train PSNR proxy (train.py:609-613), test PSNR with the reference's
-8-bit formula (renderer.py:399-401), rays/s.
+8-bit formula (renderer.py:399-401), rays/s.  --render-test (Blender scenes, train.py:861-875): after training, rank 0 evaluates
+every test view (renderer.evaluation: PSNR, SSIM, normal error, frames) into <logfolder>/imgs_test_all/ and prints one more line
+{"test_all": {"psnr", "ssim", "norm_err", "views"}}.
 """
 import argparse
 import json
@@ -41,6 +43,14 @@ from .trainer import Trainer, agree, rank_slice
 def render_images(nerf, rays, focal, chunk, noise):
     """chunk_renderer with render2completion (renderer.py:56-106) in eval mode -> rgb [n,3]"""
     return _render_images(nerf, rays, focal, chunk, noise, draw_debug=True)
+
+
+def test_all_record(res):
+    """the means of a renderer.evaluation result (stats.yaml's psnr / ssim / norm_err) and the number of views"""
+    import numpy as np
+    mean = lambda v: round(float(np.mean(v)), 6) if len(v) else None        # noqa: E731
+    return dict(psnr=mean(res["psnrs"]), ssim=mean(res["ssims"]), norm_err=mean(res["norm_errs"]) if res["norm_errs"] else 0,
+                views=len(res["psnrs"]))
 
 
 def compose_run(args, overrides):
@@ -98,6 +108,8 @@ def main(argv=None):
                     help="weak scaling: every rank takes this many rays per optimizer step (BASELINE configs[3]: 32768), "
                          "processed in num_rays chunks; default: the reference's lbatch_size split over the ranks")
     ap.add_argument("--no-config-file", action="store_true", help="do not write <basedir>/<expname>/config.yaml")
+    ap.add_argument("--render-test", action="store_true",
+                    help="Blender scenes: evaluate every test view after training into <logfolder>/imgs_test_all/ (train.py:861-875)")
     ap.add_argument("-m", "--multirun", action="store_true",
                     help="hydra multirun (README.md:10): comma-separated override values span a sweep, run job by job")
     ap.add_argument("overrides", nargs="*", help="hydra-style tokens: group=name, a.b.c=value")
@@ -125,6 +137,8 @@ def main(argv=None):
         if args.test_views is None and args.datadir:
             cfg["N_vis"] = 4
     ds = cfg["dataset"]
+    if args.render_test and ds["dataset_name"] != "blender":
+        ap.error(f"--render-test needs a Blender scene (--datadir or dataset=<scene>); dataset_name is {ds['dataset_name']}")
     params = cfg["model"]["params"]
     n_iters = args.iters if args.iters is not None else (200 if shorthand else int(params["n_iters"]))
     eval_every = args.eval_every if args.eval_every is not None else (100 if shorthand else int(cfg["vis_every"]))
@@ -255,6 +269,12 @@ def main(argv=None):
         arch["model"]["diffuse_module"]["diffuse_bias"] = nerf.model.diffuse_module.diffuse_bias
         arch["model"]["diffuse_module"]["roughness_bias"] = nerf.model.diffuse_module.roughness_bias
         nerf.save(save, arch)
+    if args.render_test and rank == 0:
+        from .dataLoader import BlenderDataset
+        from .renderer import evaluation
+        te_all = BlenderDataset(scene, split="test", downsample=float(ds["downsample_test"]), is_stack=True, N_vis=-1)
+        res = evaluation(te_all, nerf, None, None, os.path.join(logfolder, "imgs_test_all"), N_vis=-1, device=dev, noise=noise)
+        print(json.dumps(dict(test_all=test_all_record(res))), flush=True)
     if world > 1:
         dist.destroy_process_group()
     return cfg
