@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 117
+#define NMF_ABI_VERSION 118
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -698,6 +698,31 @@ int64_t nmf_ssim_workspace_bytes(int64_t n_img, int32_t H, int32_t W, int32_t C)
 int nmf_normal_err(const float* pred, const float* gt, const float* acc, int64_t n_img, int64_t n_px,
                    double* mean_out, float* err_map, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t nmf_normal_err_workspace_bytes(int64_t n_img, int64_t n_px);
+
+/* ------------------------------------------------------------------------------------------
+ * Material maps of the evaluation pass (renderer.py:440-463, modules/tensor_nerf.py:480-566, models/microfacet.py:299-316,
+ * 572,615-672), recursion level 0.  Per primary ray r with kept samples k = offsets[r] .. offsets[r+1]-1:
+ *   map_X[r] = sum_k w_k X_k + (1 - acc[r]) bg
+ * with h = heads(app_k) (the 24 -> 11 heads of nmf_heads_fwd, no feature noise), n = normals[k], v = rays[r][3:6] and
+ *   albedo    = h[0:3]
+ *   roughness = h[9] (one value, the bg term makes it 3 channels)
+ *   diffuse   = (1 - Fr) albedo E,  E[c] = sum_j conv[j][c] Y_j(n) (the 9 SH bases of modules/sh.py)
+ *   tint      = Fr brdf_rgb_k
+ *   spec      = spec_k
+ *   Fr = f0 + (1 - f0) clip(1 - |dot(-v, n)|, 0, 1)^5, f0 = h[6:9]
+ * For a sample with a bounce row q = inv[k] >= 0, spec_k / brdf_rgb_k = sum over the rays j = row_off[q] .. row_off[q+1]-1 of
+ * incoming[j] / max(cnt[q], 1) and brdf_weight[j] / max(cnt[q], 1) (index order); 0 for every other sample.
+ * app [M][24], normals [M][3], weight [M], offsets [B+1] int64, rays [B][6], head_W [11][24], head_b [11], conv [9][3],
+ * inv [M] int32 (bounce row or -1), row_off [Mb+1] int64, cnt [Mb] int32, incoming / brdf_weight [R][3], acc [B], bg [3] (device).
+ * Mb == 0 (then R == 0): the row inputs may be NULL, spec and tint are 0.
+ * out [B][15] fp32: albedo 0-2 | roughness 3-5 | diffuse 6-8 | tint 9-11 | spec 12-14.  One launch; a lane group per ray sums its
+ * samples in a fixed order (bit-identical from run to run); samples with w == 0 are skipped; no per-sample value is stored.
+ * ---------------------------------------------------------------------------------------- */
+int nmf_material_maps(const float* app, const float* normals, const float* weight, const int64_t* offsets, int64_t B, int64_t M,
+                      const float* rays, const float* head_W, const float* head_b, float diffuse_mul, float diffuse_bias,
+                      float tint_bias, float f0_bias, float rough_bias, const float* conv, const int32_t* inv,
+                      const int64_t* row_off, const int32_t* cnt, int64_t Mb, const float* incoming, const float* brdf_weight,
+                      int64_t R, const float* acc, const float* bg, float* out, void* stream);
 
 #ifdef __cplusplus
 }

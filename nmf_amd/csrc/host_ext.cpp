@@ -359,6 +359,23 @@ Tensor brdf_mlp_pack(const std::vector<Tensor>& w, const OT& into, int64_t strea
     return img;
 }
 
+// ---- material maps of the evaluation pass (nmf_material_maps) -----------------------------------------------------------
+// -> [B,15]: albedo | roughness | diffuse | tint | spec, 3 columns each
+Tensor material_maps(const Tensor& app, const Tensor& normals, const Tensor& w, const Tensor& offsets, const Tensor& rays,
+                     const Tensor& W, const Tensor& b, const std::vector<double>& hp, const Tensor& conv, const Tensor& inv,
+                     const Tensor& row_off, const Tensor& cnt, const Tensor& incoming, const Tensor& brdf_weight, const Tensor& acc,
+                     const Tensor& bg, int64_t stream) {
+    TimedScope _ts(__func__, stream);
+    if (hp.size() != 5) fail("material_maps: hp = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)");
+    const int64_t B = offsets.size(0) - 1, M = app.size(0), Mb = row_off.size(0) - 1, R = incoming.size(0);
+    Tensor o = fe(app, {B, 15});
+    check(nmf_material_maps(f32(app), f32(normals), f32(w), i64(offsets), B, M, f32(rays), f32(W), f32(b), (float)hp[0], (float)hp[1],
+                            (float)hp[2], (float)hp[3], (float)hp[4], f32(conv), i32(inv), i64(row_off), i32(cnt), Mb, f32(incoming),
+                            f32(brdf_weight), R, f32(acc), f32(bg), out(o), st(stream)),
+          "nmf_material_maps");
+    return o;
+}
+
 Tensor heads_fwd(const Tensor& feat, const Tensor& W, const Tensor& b, const std::vector<double>& hp, int64_t stream) {
     TimedScope _ts(__func__, stream);
     if (hp.size() != 5) fail("heads_fwd: hp = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)");
@@ -1223,6 +1240,7 @@ PYBIND11_MODULE(_nmf_host, m) {
     m.def("brdf_mlp_bwd_sets", &brdf_mlp_bwd_sets, py::arg("w"), py::arg("sets"), py::arg("grads"), py::arg("max_workgroups"), py::arg("stream"),
           py::arg("image") = py::none());
     m.def("heads_fwd", &heads_fwd);
+    m.def("material_maps", &material_maps);
     m.def("ggx_rays_fwd", &ggx_rays_fwd);
     m.def("shade_mix_fwd", &shade_mix_fwd);
     m.def("bounce_index", &bounce_index, py::arg("counts"), py::arg("xyzt"), py::arg("stream"), py::arg("pub") = 0, py::arg("pub_seq") = 0,
@@ -1276,7 +1294,8 @@ PYBIND11_MODULE(_nmf_host, m) {
         .def("train_backward", &StepCore::train_backward)
         .def("has_pending", &StepCore::has_pending)
         .def("drop_pending", &StepCore::drop_pending)
-        .def("render", &StepCore::render)
+        .def("render", &StepCore::render, py::arg("rays"), py::arg("focal"), py::arg("noise"), py::arg("want_maps"),
+             py::arg("want_materials") = false)
         .def("begin_step", &StepCore::begin_step)
         .def("join_early_env", &StepCore::join_early_env)
         .def("env_was_used", &StepCore::env_was_used)

@@ -236,7 +236,10 @@ class StepCore {
     // ---- one evaluation chunk (TrainPass.render_chunk) ------------------------------------------------------------------
     // want_maps: also the two per-ray maps of the reference's evaluation branch that need no dense appearance pass
     // (modules/tensor_nerf.py:480-501): depth = sum_k w_k z_k, world_normal = acc * sum_k w_k n_k + (1 - acc)
-    py::object render(const Tensor& rays, double focal, py::object noise, bool want_maps) {
+    // want_materials: also the material maps of level 0 (renderer.py:440-463) as one [B,15] block (nmf_material_maps: albedo |
+    // roughness | diffuse | tint | spec), appended last.  Queued after the whole level tree: the appearance query over all kept
+    // samples, then one launch; no noise is drawn and no launch the other outputs come from changes.
+    py::object render(const Tensor& rays, double focal, py::object noise, bool want_maps, bool want_materials = false) {
         begin(noise);
         eval_z_ = want_maps;
         std::unique_ptr<CoreLevel> t;
@@ -248,15 +251,47 @@ class StepCore {
         }
         eval_z_ = false;
         if (t->M == 0) return py::none();
-        if (!want_maps) return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples);
+        OT mats;
+        if (want_materials) mats = material_maps_(*t);
+        if (!want_maps) {
+            if (mats.has_value()) return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples, *mats);
+            return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples);
+        }
         if (!t->S.z.has_value() || !t->nr.has_value()) throw std::runtime_error("Unsupported: evaluation maps need the sampler's z values and dense normals");
         Tensor depth = segment_sum(t->S.z->view({t->M, 1}), OT(t->w), t->offsets, t->B, 1, main_stream).view({t->B});
         Tensor wn = segment_sum(*t->nr, OT(t->w), t->offsets, t->B, 1, main_stream);
         Tensor a = t->acc.unsqueeze(1);
         Tensor world_normal = a * wn + (1.0 - a);
+        if (mats.has_value()) return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples, depth, world_normal, *mats);
         return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples, depth, world_normal);
     }
 
+  private:
+    // the material maps of level 0: appearance features of every kept sample (the forward query with appearance only), then
+    // nmf_material_maps over the samples, their dense normals and the level's bounce rows
+    Tensor material_maps_(CoreLevel& t) {
+        if (!t.nr.has_value() || t.sparse_n || t.lvl != 0)
+            throw std::runtime_error("Unsupported: material maps need the dense normals of level 0");
+        if (!t.brdf.has_value() || !t.incoming.defined() || t.incoming.size(0) != t.R || !t.conv.defined() || !head_W.defined())
+            throw std::runtime_error("Unsupported: material maps need the bounce rows' incoming radiance and BRDF weights");
+        const int64_t M = t.M, B = t.B;
+        Tensor xyzt = t.S.xyzt.narrow(0, 0, M).contiguous();
+        Tensor app = *std::get<4>(vm_query_fwd(vm_p, xyzt, fw(f_dpk, dpk), fw(f_dlk, dlk), fw(f_apl, apl), fw(f_ali, ali), basis, false,
+                                               false, true, false, main_stream));
+        Tensor rays = t.S.rays.narrow(0, 0, B).contiguous();
+        Tensor nr = t.nr->contiguous(), w = t.w.contiguous(), inv = t.inv.narrow(0, 0, M).contiguous();
+        Tensor incoming = t.incoming.contiguous(), brdf = t.brdf->contiguous(), conv = t.conv.contiguous();
+        Tensor maps = material_maps(app, nr, w, t.offsets.contiguous(), rays, head_W, head_b, head_p, conv, inv, t.row_off.contiguous(),
+                                    t.cnt32.contiguous(), incoming, brdf, t.acc.contiguous(), t.bg.contiguous(), main_stream);
+        if (!trace_.is_none()) {       // tests: the inputs of the maps, for a restatement in float64
+            trace_put("mm_app0", app); trace_put("mm_normals0", nr); trace_put("mm_w0", w); trace_put("mm_offsets0", t.offsets);
+            trace_put("mm_rays0", rays); trace_put("mm_inv0", inv); trace_put("mm_row_off0", t.row_off); trace_put("mm_cnt0", t.cnt32);
+            trace_put("mm_incoming0", incoming); trace_put("mm_brdf0", brdf); trace_put("mm_conv0", conv); trace_put("mm_acc0", t.acc);
+        }
+        return maps;
+    }
+
+  public:
     bool env_table_backward_queued() const { return early_env_done; }
     bool env_was_used() const { return used_env; }
     void begin_step() { used_env = false; early_env_done = false; env_streams_.clear(); }

@@ -454,10 +454,12 @@ class TrainPass:
 
     # ---- evaluation: forward only ---------------------------------------------------------------------------------------
     @torch.no_grad()
-    def render_chunk(self, rays, focal, noise, want_maps=False):
+    def render_chunk(self, rays, focal, noise, want_maps=False, want_materials=False):
         """`TensorNeRF.forward(rays, focal, bg_col=white, is_train=False, draw_debug=False)` as one C++ call:
         -> (rgb_map [b,3], acc_map [b], b = rays the sampler kept, n_samples) + (depth [b], world_normal [b,3]) with want_maps (the two
-        maps of the reference's evaluation branch that need no dense appearance pass, modules/tensor_nerf.py:480-501).  Raises
+        maps of the reference's evaluation branch that need no dense appearance pass, modules/tensor_nerf.py:480-501) + a dict
+        {albedo, roughness, diffuse, tint, spec} of [b,3] maps with want_materials (level 0, renderer.py:440-463: one appearance query
+        over the kept samples and nmf_material_maps, queued after everything else; the other outputs keep their bits).  Raises
         Unsupported (configuration, no sample, no bounce row): the caller renders that chunk through the module."""
         nerf = self.nerf
         if not self.supported():
@@ -469,14 +471,19 @@ class TrainPass:
             core = self.core()
             self._core_sync(rays.device, focal, False)
             try:
-                out = core.render(rays, float(focal), noise, bool(want_maps))
+                out = core.render(rays, float(focal), noise, bool(want_maps), bool(want_materials))
             except RuntimeError as e:
                 if "Unsupported" in str(e):
                     raise Unsupported(str(e)) from None
                 raise
             if out is None:
                 raise Unsupported("no sample")
-            return (out[0], out[1], out[2], list(out[3])) + ((out[4], out[5]) if want_maps else ())
+            res = (out[0], out[1], out[2], list(out[3])) + ((out[4], out[5]) if want_maps else ())
+            if want_materials:
+                from .hip import MATERIAL_MAPS
+                block = out[-1]
+                res = res + ({k: block[:, 3 * i:3 * i + 3] for i, k in enumerate(MATERIAL_MAPS)},)
+            return res
         finally:
             for m in mods:
                 m.end_pass()

@@ -74,6 +74,7 @@ EXPORTS = [
     "nmf_loss_mix_fwd", "nmf_loss_mix_bwd", "nmf_loss_head", "nmf_loss_head_workspace_bytes", "nmf_bg_adjoint", "nmf_vm_query_bwd_segments", "nmf_vm_query_bwd_segments_clean", "nmf_vm_bwd_clean_bytes", "nmf_vm_unpack_density_grad_l1", "nmf_vm_bin_plan", "nmf_vm_bin_plan_bytes", "nmf_vm_walk_workspace_bytes", "nmf_vm_query_bwd_planned", "nmf_sh_project",
     "nmf_retrace_scores", "nmf_argsort_f32", "nmf_argsort_workspace_bytes", "nmf_topk_select", "nmf_topk_select_workspace_bytes", "nmf_alpha_coarse", "nmf_alpha_coarse_words", "nmf_bounce_index_select", "nmf_bounce_prep_fwd_heads", "nmf_bounce_prep_heads_bwd", "nmf_multi_copy",
     "nmf_ssim", "nmf_ssim_workspace_bytes", "nmf_normal_err", "nmf_normal_err_workspace_bytes",
+    "nmf_material_maps",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -1287,6 +1288,32 @@ def normal_err(pred, gt, acc, return_map=False):
     _check(_lib.nmf_normal_err(_p(P, torch.float32), _p(G, torch.float32), _p(Acc, torch.float32), C.c_int64(n),
                                C.c_int64(n_px), _p(out), _p(emap), _p(ws), C.c_int64(ws.numel()), _stream()), "nmf_normal_err")
     return (out, emap.reshape(acc.shape)) if return_map else out
+
+
+# ---- material maps of the evaluation pass (renderer.py:440-463) ------------------------------------------------------
+MATERIAL_MAPS = ("albedo", "roughness", "diffuse", "tint", "spec")          # the [B,15] block of nmf_material_maps, 3 columns each
+
+
+def material_maps(app, normals, weight, offsets, rays, head_W, head_b, head_p, conv, acc, bg, inv=None, row_off=None, cnt=None,
+                  incoming=None, brdf_weight=None):
+    """nmf_material_maps: the level-0 material maps of B rays from their M kept samples -> fp32 [B,15] (albedo | roughness |
+    diffuse | tint | spec, 3 columns each).  app [M,24], normals [M,3], weight [M], offsets int64 [B+1], rays [B,6], head_W [11,24],
+    head_b [11], head_p = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias), conv [9,3], acc [B], bg [3]; the bounce rows
+    inv int32 [M], row_off int64 [Mb+1], cnt int32 [Mb], incoming / brdf_weight [R,3] (all None: no row, spec and tint are 0)."""
+    B, M = offsets.shape[0] - 1, app.shape[0]
+    Mb = 0 if row_off is None else row_off.shape[0] - 1
+    R = 0 if incoming is None else incoming.shape[0]
+    if len(head_p) != 5:
+        raise NmfHipError("material_maps: head_p = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)")
+    out = torch.empty((B, 15), dtype=torch.float32, device=offsets.device)
+    hp = [C.c_float(float(v)) for v in head_p]
+    _check(_lib.nmf_material_maps(_p(app, torch.float32), _p(normals, torch.float32), _p(weight, torch.float32),
+                                  _p(offsets, torch.int64), C.c_int64(B), C.c_int64(M), _p(rays, torch.float32),
+                                  _p(head_W, torch.float32), _p(head_b, torch.float32), *hp, _p(conv, torch.float32),
+                                  _p(inv, torch.int32), _p(row_off, torch.int64), _p(cnt, torch.int32), C.c_int64(Mb),
+                                  _p(incoming, torch.float32), _p(brdf_weight, torch.float32), C.c_int64(R),
+                                  _p(acc, torch.float32), _p(bg, torch.float32), _p(out), _stream()), "nmf_material_maps")
+    return out
 
 
 # ---- host-side fast path ---------------------------------------------------------------------------------------------

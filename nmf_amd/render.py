@@ -12,6 +12,8 @@ Prints one JSON line: frames, rays/s (render to completion, eval_batch_size rays
 
 --eval-dir (the reference's render_only + render_test, train.py:167-180) then evaluates the views with renderer.evaluation:
 frames, mean.txt and stats.yaml go to DIR, and the line gains ssim, norm_err and the evaluation's render / metric seconds.
+--material-maps adds the material maps of every view (renderer.py:433-463): albedo/, roughness/, tint/, diffuse/ PNGs, spec/ and
+rgbd/ (depth) EXRs.
 """
 import argparse
 import json
@@ -64,9 +66,13 @@ def main(argv=None):
     ap.add_argument("--chunk", type=int, default=None, help="rays per chunk (default: the model's eval_batch_size)")
     ap.add_argument("--eval-dir", default=None,
                     help="with --datadir: evaluate the test views (PSNR, SSIM, normal error) into this directory")
+    ap.add_argument("--material-maps", action="store_true",
+                    help="with --eval-dir: also write the material maps (albedo/, roughness/, tint/, diffuse/ PNGs, spec/ and rgbd/ EXRs)")
     args = ap.parse_args(argv)
     if args.eval_dir and not args.datadir:
         ap.error("--eval-dir needs --datadir (ground truth of a Blender scene)")
+    if args.material_maps and not args.eval_dir:
+        ap.error("--material-maps needs --eval-dir")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
     gt = None
@@ -101,7 +107,8 @@ def main(argv=None):
         from .renderer import evaluation
         from .train import test_all_record
         t0 = time.perf_counter()
-        res = evaluation(ds, nerf, None, None, args.eval_dir, N_vis=-1, device=dev, noise=noise)
+        res = evaluation(ds, nerf, None, None, args.eval_dir, N_vis=-1, device=dev, noise=noise,
+                         **(dict(material_maps=True) if args.material_maps else {}))
         rec_all = test_all_record(res)
         rec.update(ssim=rec_all["ssim"], norm_err=rec_all["norm_err"],
                    eval_seconds=dict(total=round(time.perf_counter() - t0, 4), render=round(res["seconds"]["render"], 4),

@@ -61,14 +61,20 @@ def psnr_8bit(pred, gt):
 @torch.no_grad()
 def render_images(nerf, rays, focal, chunk=None, noise=None, keys=("rgb_map",), **kw):
     """evaluation render (renderer.py:119-170 without the random permutation): eval_batch_size rays per chunk, rendered
-    to completion, is_train=False"""
+    to completion, is_train=False.  keys may name the material maps MATERIAL_KEYS (renderer.py:440-463, [N,3] each): the fused
+    pass forms them (TrainPass.render_chunk(want_materials=True)); without it the whole call renders through the module with
+    draw_debug=True, and a chunk the fused pass does not support through the module with draw_debug=True."""
     chunk = chunk or nerf.eval_batch_size
     kw.setdefault("draw_debug", False)
     module_kw = dict(bg_col=torch.ones(3, device=rays.device), is_train=False, ndc_ray=False, noise=noise, **kw)
     tensorf = nerf
     maps = bool(set(keys) & {"depth", "world_normal"})
-    fast = _eval_pass(nerf) if (rays.is_cuda and not kw["draw_debug"] and set(keys) <= {"rgb_map", "acc_map", "depth", "world_normal"}
+    mats = bool(set(keys) & set(MATERIAL_KEYS))
+    fast = _eval_pass(nerf) if (rays.is_cuda and not kw["draw_debug"]
+                                and set(keys) <= {"rgb_map", "acc_map", "depth", "world_normal", *(MATERIAL_KEYS if mats else ())}
                                 and len(kw) == 1) else None
+    if mats and fast is None:
+        module_kw["draw_debug"] = True            # the module's evaluation branch forms the maps (modules/tensor_nerf.py:480-566)
     if fast is not None:
         from .fast_step import Unsupported
 
@@ -80,15 +86,20 @@ def render_images(nerf, rays, focal, chunk=None, noise=None, keys=("rgb_map",), 
                         from .noise import DeviceNoise
                         nerf._noise = DeviceNoise(pending.device, seed=20211200)
                     nz = nerf._noise
-                out = fast.render_chunk(pending, focal_, nz, want_maps=maps)
+                out = fast.render_chunk(pending, focal_, nz, want_maps=maps, **(dict(want_materials=True) if mats else {}))
             except Unsupported:
-                return nerf(pending, focal_, **(dict(module_kw, draw_debug=True) if maps else module_kw))
+                return nerf(pending, focal_, **(dict(module_kw, draw_debug=True) if (maps or mats) else module_kw))
             ims_ = dict(rgb_map=out[0], acc_map=out[1])
             if maps:
                 ims_.update(depth=out[4], world_normal=out[5])
+            if mats:
+                ims_.update(out[-1])
             return ims_, dict(rays_kept=out[2], n_samples=out[3])
     ims, _ = chunk_renderer(rays, tensorf, focal, keys=keys, chunk=chunk, render2completion=True, **module_kw)
     return ims["rgb_map"] if tuple(keys) == ("rgb_map",) else ims
+
+
+MATERIAL_KEYS = ("albedo", "roughness", "diffuse", "tint", "spec")
 
 
 def _eval_pass(nerf):
@@ -111,24 +122,46 @@ def _png(path, arr):
     Image.fromarray(np.ascontiguousarray(arr)).save(path)
 
 
+def map_to_8bit(x):
+    """the reference's 8-bit conversion of a map in [0, 1] (renderer.py:440-463: (255 * x).astype(uint8), a truncation), clipped to
+    [0, 1] first: astype(uint8) wraps a value outside [0, 255] around (a spec-heavy tint above 1 would come out dark)"""
+    return (np.clip(np.asarray(x, dtype=np.float32), 0.0, 1.0) * 255).astype(np.uint8)
+
+
+MATERIAL_DIRS = ("albedo", "roughness", "tint", "diffuse", "spec", "rgbd")
+
+
+def write_material_maps(savePath, name, ims, H, W):
+    """renderer.py:433-463 for the material maps: albedo/, roughness/, tint/, diffuse/ 8-bit PNGs (map_to_8bit), spec/ and rgbd/
+    (depth) float EXRs (nmf_amd/exr.py)"""
+    from . import exr
+    for key in ("albedo", "roughness", "tint", "diffuse"):
+        _png(os.path.join(savePath, key, name + ".png"), map_to_8bit(ims[key].reshape(H, W, 3).cpu().numpy()))
+    exr.imwrite(os.path.join(savePath, "spec", name + ".exr"), ims["spec"].reshape(H, W, 3).cpu().numpy())
+    exr.imwrite(os.path.join(savePath, "rgbd", name + ".exr"), ims["depth"].reshape(H, W).cpu().numpy())
+
+
 @torch.no_grad()
 def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", N_samples=-1, white_bg=False, ndc_ray=False,
-             compute_extra_metrics=True, device="cuda", noise=None, **kw):
+             compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, **kw):
     """renderer.py:195-510 for the outputs the fused eval pass produces.  Per view of `iterator()` ((idx, im_idx, rays,
     gt_rgb [H,W,3] or None)): PSNR of the 8-bit prediction (psnr_8bit), with compute_extra_metrics its SSIM against the
     unclipped ground truth (renderer.py:403-404, nmf_ssim), and the normal error (renderer.py:357-390, nmf_normal_err) when
     the data set has a normal map for the view.  Writes {prtx}{idx:03d}.png, world_normal/, acc_map/ and err/ PNGs with the
     reference's 8-bit conversions, {prtx}mean.txt ([psnr, ssim, nan, nan]: LPIPS is not computed; [psnr] without extra
-    metrics) and stats{prtx}.yaml (psnr, ssim, norm_err).  LPIPS, videos, EXR outputs and the debug maps are not produced.
+    metrics) and stats{prtx}.yaml (psnr, ssim, norm_err).  LPIPS, videos, the EXR frame and normal/ are not produced.
     `renderer`, `N_samples` and `white_bg` are accepted for the reference's call shape (the model's own background and
-    sample budget are used).  -> dict(psnrs, norm_errs, ssims, seconds=dict(render, metrics))."""
+    sample budget are used).  material_maps: each view also renders depth and the material maps (render_images' MATERIAL_KEYS)
+    and writes albedo/, roughness/, tint/, diffuse/ PNGs (map_to_8bit: the reference's truncation, clipped to [0, 1] first where
+    its astype(uint8) would wrap), spec/ and rgbd/ (depth) EXRs, renderer.py:433-463.
+    -> dict(psnrs, norm_errs, ssims, seconds=dict(render, metrics))."""
     from . import hip
     if ndc_ray:
         raise NotImplementedError("evaluation: ndc rays are not used by model=microfacet_tensorf2")
     W, H = test_dataset.img_wh
     focal = float(test_dataset.fx)
     if savePath is not None:
-        for sub in ("", "world_normal", "acc_map", "err"):
+        for sub in ("", "world_normal", "acc_map", "err") + (MATERIAL_DIRS if material_maps else ()):
             os.makedirs(os.path.join(savePath, sub), exist_ok=True)
     has_normal = getattr(test_dataset, "has_normal", None)
     acc_maps = getattr(test_dataset, "acc_maps", [])
@@ -139,7 +172,8 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
     for idx, im_idx, rays, gt_rgb in iterator():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ims = render_images(tensorf, rays.to(device), focal, noise=noise, keys=("rgb_map", "acc_map", "world_normal"))
+        keys = ("rgb_map", "acc_map", "world_normal") + (("depth",) + MATERIAL_KEYS if material_maps else ())
+        ims = render_images(tensorf, rays.to(device), focal, noise=noise, keys=keys)
         rgb = ims["rgb_map"].reshape(H, W, 3)
         acc = ims["acc_map"].reshape(H, W)
         wn = ims["world_normal"].reshape(H, W, 3)
@@ -169,6 +203,8 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
             if gt_rgb is not None:
                 err = (rgb.clip(0, 1) - gt.clip(0, 1)) + 0.5
                 _png(os.path.join(savePath, "err", f"{prtx}{idx:03d}.png"), (err.clamp(0, 1).cpu().numpy() * 255).astype("uint8"))
+            if material_maps:
+                write_material_maps(savePath, f"{prtx}{idx:03d}", ims, H, W)
     tensorf.train(was_training)
 
     final_stats = {}
@@ -192,7 +228,7 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
 
 @torch.no_grad()
 def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=5, prtx="", N_samples=-1, white_bg=False,
-               ndc_ray=False, compute_extra_metrics=True, device="cuda", noise=None, **kw):
+               ndc_ray=False, compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, **kw):
     """renderer.py:513-560: every max(N // N_vis, 1)-th view of a stacked test set (all views with N_vis < 0) through
     `evaluate`; the call shape of train.py:863-875."""
     n = test_dataset.all_rays.shape[0]
@@ -206,4 +242,5 @@ def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=
             yield idx, im_idx, rays, (test_dataset.all_rgbs[im_idx] if have_gt else None)
 
     return evaluate(iterator, test_dataset, tensorf, renderer, savePath, prtx=prtx, N_samples=N_samples, white_bg=white_bg,
-                    ndc_ray=ndc_ray, compute_extra_metrics=compute_extra_metrics, device=device, noise=noise, **kw)
+                    ndc_ray=ndc_ray, compute_extra_metrics=compute_extra_metrics, device=device, noise=noise,
+                    material_maps=material_maps, **kw)

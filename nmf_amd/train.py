@@ -110,10 +110,15 @@ def main(argv=None):
     ap.add_argument("--no-config-file", action="store_true", help="do not write <basedir>/<expname>/config.yaml")
     ap.add_argument("--render-test", action="store_true",
                     help="Blender scenes: evaluate every test view after training into <logfolder>/imgs_test_all/ (train.py:861-875)")
+    ap.add_argument("--material-maps", action="store_true",
+                    help="with --render-test: also write the material maps of every test view (albedo/, roughness/, tint/, diffuse/, "
+                         "spec/, rgbd/)")
     ap.add_argument("-m", "--multirun", action="store_true",
                     help="hydra multirun (README.md:10): comma-separated override values span a sweep, run job by job")
     ap.add_argument("overrides", nargs="*", help="hydra-style tokens: group=name, a.b.c=value")
     args = ap.parse_args(argv)
+    if args.material_maps and not args.render_test:
+        ap.error("--material-maps needs --render-test")
     for o in args.overrides:
         if "=" not in o:
             ap.error(f"'{o}': overrides are key=value tokens (hydra syntax)")
@@ -273,7 +278,8 @@ def main(argv=None):
         from .dataLoader import BlenderDataset
         from .renderer import evaluation
         te_all = BlenderDataset(scene, split="test", downsample=float(ds["downsample_test"]), is_stack=True, N_vis=-1)
-        res = evaluation(te_all, nerf, None, None, os.path.join(logfolder, "imgs_test_all"), N_vis=-1, device=dev, noise=noise)
+        res = evaluation(te_all, nerf, None, None, os.path.join(logfolder, "imgs_test_all"), N_vis=-1, device=dev, noise=noise,
+                         **(dict(material_maps=True) if args.material_maps else {}))
         print(json.dumps(dict(test_all=test_all_record(res))), flush=True)
     if world > 1:
         dist.destroy_process_group()
