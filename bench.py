@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the microfacet_tensorf2 hot path on MI355X (see BASELINE.json / SURVEY.md 8d).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--rays-per-gpu R] [--grid G] [--mode train|infer] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--rays-per-gpu R] [--grid G] [--mode train|infer] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 launches itself as N ranks under torch.distributed.run (one process per GPU, RCCL); when the
 driver has already done that (WORLD_SIZE set) the process is one of the ranks.
@@ -14,9 +14,12 @@ SURVEY F9).  Ray batches are resident in HBM before the timed region.  Rank 0 pr
 
 `--mode infer`: a step is one full 800x800 frame rendered to completion in eval_batch_size chunks (BASELINE configs[4]).
 
-At N = 1 the default run also reports, outside the timed region (`extras`): inference rays/s of a full frame, the training
-step at the final 300^3 grid, the early phase (1000 re-traced rays), the 32768-ray step of configs[3], and the bf16-table
-variant (configs[1]) next to f32.
+A plain run does only what the line's headline needs: it sets up, warms up, times the K steps (the dominant kernel of the
+step timed inside them: `roofline`), writes --dump-outputs and prints the line.  `--full` adds, after the timed steps: the
+per-kernel table of 30 instrumented steps (`roofline.per_kernel`, `roofline.step`) and, at N = 1, the CPU baseline and the
+`extras` legs -- inference rays/s of a full frame, the training step at the final 300^3 grid, the early phase (1000 re-traced
+rays), the 32768-ray step of configs[3], the bf16-table variant (configs[1]) next to f32 and `psnr_at_iter`
+(`--no-extras` / `--no-cpu-baseline` leave those two out again).
 """
 import argparse
 import json
@@ -221,6 +224,14 @@ def per_kernel_table(timing, steps, sz, n_params, counters):
     return rows
 
 
+def chunk_sizes(fast, nerf):
+    """the sizes kernel_models() prices, of the last chunk the trainer's C++ pass ran"""
+    ls = fast.last_sizes
+    return dict(B=int(ls["rays"]), M0=int(ls["n_samples"][0]), M1=int(ls["n_samples"][1]) if len(ls["n_samples"]) > 1 else 0,
+                R0=int(ls["n_rays"][0]), R1=int(ls["n_rays"][1]) if len(ls["n_rays"]) > 1 else 0,
+                Mb0=int(ls["n_rows"][0]), Mb1=int(ls["n_rows"][1]) if len(ls["n_rows"]) > 1 else 0, N=int(nerf.sampler.nSamples))
+
+
 def step_bytes(sz, grid, n_params):
     """SURVEY 8(d) bytes of one optimizer step (every tap charged to HBM, dense appearance and normals on every sample) and the
     bytes the pass needs after sparse appearance / sparse normals (values for the re-traced samples, appearance + normals on the
@@ -256,7 +267,7 @@ def cpu_baseline(budget_s=150.0, warm=1, timed=3):
     loss), one thread per physical core, one warm-up step and up to three timed steps in each phase -- early (1000 rays
     re-traced, the first 19 chunks after every (re)start) and steady state (all re-traced, what `value` is quoted on) --
     bounded to ~`budget_s` seconds of CPU work: a phase stops timing once its share of the budget is spent.
-    `--cpu-baseline-steps 3,10` is SURVEY 8(d)'s full protocol (3 warm-up + 10 timed steps per phase, ~6 minutes of host time,
+    `--full --cpu-baseline-steps 3,10` is SURVEY 8(d)'s full protocol (3 warm-up + 10 timed steps per phase, ~6 minutes of host time,
     no budget): run once per round and kept in profiles/."""
     import torch
     from nmf_amd import synthetic
@@ -301,7 +312,7 @@ def cpu_baseline(budget_s=150.0, warm=1, timed=3):
                 early_phase=out["early"], steady_state=st,
                 protocol=f"{warm}+{timed} steps per phase within a {budget_s} s budget" if budget_s else f"{warm}+{timed} steps per phase (SURVEY 8d)",
                 protocol_full="profiles/r04_cpu_baseline_3_10.json (SURVEY 8d's 3 warm-up + 10 timed steps per phase on the GPU box's host: "
-                              "213 rays/s steady state, 634 rays/s early phase; `python bench.py --cpu-baseline-steps 3,10`)")
+                              "213 rays/s steady state, 634 rays/s early phase; `python bench.py --full --cpu-baseline-steps 3,10`)")
 
 
 LINE_LIMIT = 6144           # bytes: the driver keeps an 8 KB tail of stdout and parses the last line out of it (round 5's 21 KB line was not parsed)
@@ -949,8 +960,8 @@ def extras(device, params, focal, main_ms=None, main_rays=None):
     # were built, not the table type: DESIGN 0.2)
     legs = {}
     for name in ("bf16", "f32"):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--table-dtype", name, "--steps", "80", "--warmup", "20",
-                            "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--table-dtype", name, "--steps", "80", "--warmup", "20"],
+                           capture_output=True, text=True, timeout=900)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         legs[name] = json.loads(lines[-1]) if r.returncode == 0 and lines else None
     if legs["bf16"] is None or legs["f32"] is None:
@@ -966,7 +977,7 @@ def extras(device, params, focal, main_ms=None, main_rays=None):
     return out
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -979,9 +990,12 @@ def main():
     ap.add_argument("--table-dtype", choices=("f32", "bf16"), default="f32")
     ap.add_argument("--retrace", type=int, default=None,
                     help="max_retrace_rays (default: every secondary ray = the steady state; 1000 = the early phase)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-steps", default=None, help="W,K: W warm-up + K timed CPU steps per phase, no time budget")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything beyond the headline figure: the per-kernel table of 30 instrumented "
+                         "steps and, at --gpus 1, the CPU baseline and the extras legs (minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-baseline-steps", default=None, help="--full: W,K: W warm-up + K timed CPU steps per phase, no time budget")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extras legs")
     ap.add_argument("--contexts", type=int, default=None, help="chunk contexts of a multi-chunk step (default: NMF_CHUNK_CONTEXTS or 2; 1 = sequential)")
     ap.add_argument("--detail-dir", default=None, help=f"where {DETAIL_FILE} (the full result: per-kernel table, notes, every leg) is written; default: next to bench.py")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -993,7 +1007,14 @@ def main():
     ap.add_argument("--core", action="append", default=[], metavar="ATTR=0|1",
                     help="A/B only: a switch of the C++ pass (csrc/step_core.inc: env_split, overlap ...) set before the warm-up; "
                          "named in config.core_switches")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
+    if args.cpu_baseline_steps and not args.full:
+        ap.error("--cpu-baseline-steps needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -1159,10 +1180,10 @@ def main():
     chunks_per_step = -(-args.rays_per_gpu // chunk_rays)
     if min(timer.rebuilds.values()) < args.steps:
         raise SystemExit(f"derived tables were not rebuilt every step: {timer.rebuilds} for {args.steps} steps")
-    # ---- after the timed region: every kernel launch of the step timed (events on the launching stream), 30 more steps
+    # ---- after the timed region (--full): every kernel launch of the step timed (events on the launching stream), 30 more steps
     table, sizes, n_params = None, None, sum(p.numel() for p in nerf.parameters() if p.requires_grad)
-    main_stream_us = None
-    if timed_calls:                       # (every rank: the steps contain the gradient all-reduce)
+    main_stream_us = wall_inst_us = None
+    if timed_calls and args.full:         # (every rank: the steps contain the gradient all-reduce)
         n_inst = 30
         main_id = torch.cuda.current_stream().cuda_stream
         sync()
@@ -1174,23 +1195,22 @@ def main():
         wall_inst_us = 1e6 * (time.perf_counter() - t_inst) / n_inst
         if f"@{main_id}" in timing:
             main_stream_us = 1e3 * timing[f"@{main_id}"][0] / n_inst
-        ls = trainer.fast.last_sizes
-        sizes = dict(B=int(ls["rays"]), M0=int(ls["n_samples"][0]), M1=int(ls["n_samples"][1]) if len(ls["n_samples"]) > 1 else 0,
-                     R0=int(ls["n_rays"][0]), R1=int(ls["n_rays"][1]) if len(ls["n_rays"]) > 1 else 0,
-                     Mb0=int(ls["n_rows"][0]), Mb1=int(ls["n_rows"][1]) if len(ls["n_rows"]) > 1 else 0, N=int(nerf.sampler.nSamples))
+        sizes = chunk_sizes(trainer.fast, nerf)
         # (sizes are those of ONE chunk; the table is per chunk when a step has several)
         table = per_kernel_table(timing, n_inst * chunks_per_step, sizes, n_params, counters_summary()) if rank == 0 else None
+    elif timed_calls:                     # (a plain run: the dominant kernel alone, at the sizes of the last timed step)
+        sizes = chunk_sizes(trainer.fast, nerf)
     if rank == 0:
         ctr = counters_summary()
         ctr_meta = {k: ctr.get(k) for k in ("tag", "commit", "command")} if ctr else None
-        roof = {"note": "the host extension with kernel timing is not available: no per-kernel table"}
-        if table:
-            dname = dominant if dominant in table else next(k_ for k_ in table if not k_.startswith("group:"))
-            drow = table[dname]
+        roof = {"note": "no dominant kernel was timed (it is found in the last warm-up steps); per-kernel table: --full" if timed_calls
+                else "the host extension with kernel timing is not available: no per-kernel table"}
+        if table or (dom_live and sizes):
+            dname = dominant if (not table or dominant in table) else next(k_ for k_ in table if not k_.startswith("group:"))
             models = kernel_models(sizes, n_params)
             bound, work, peak, unit = models.get(dname, ("latency", None, None, None))
             live_us = 1e3 * dom_live[0] / max(dom_live[1], 1) if dom_live else None          # per launch, inside the timed region
-            launches_per_chunk = dom_live[1] / (args.steps * chunks_per_step) if dom_live else drow["launches_per_step"]
+            launches_per_chunk = dom_live[1] / (args.steps * chunks_per_step) if dom_live else table[dname]["launches_per_step"]
             # achieved = useful work of one launch / that launch's duration (launches of different sizes: work and time are both
             # summed over the launches of a chunk, i.e. work per chunk / (launches per chunk x average launch duration))
             achieved = work / (launches_per_chunk * live_us * 1e-6) if (work and live_us) else None
@@ -1199,7 +1219,7 @@ def main():
             ms_step = 1e3 * dt_max / args.steps
             ck = (ctr or {}).get("kernels", {}).get(counter_key(dname), {}) if ctr else {}
             extra = issued_beside(dname, sizes)
-            dev_sum = round(sum(r["us_per_step"] for k_, r in table.items() if not k_.startswith("group:")), 1)
+            dev_sum = round(sum(r["us_per_step"] for k_, r in table.items() if not k_.startswith("group:")), 1) if table else None
             roof = {
                 # the dominant KERNEL of the step by summed device time, found in the warm-up and timed with HIP events on its
                 # launching stream INSIDE the timed region; frac = useful work / duration / peak (kernel_models())
@@ -1220,7 +1240,7 @@ def main():
                          # the main stream carries the dependency chain of the step (side streams only ever run next to it): the share
                          # of the wall time in which a kernel of the chain is executing
                          # (both from the instrumented steps: an event pair around every launch stretches them)
-                         "wall_us_instrumented": round(wall_inst_us, 1),
+                         "wall_us_instrumented": round(wall_inst_us, 1) if wall_inst_us else None,
                          "critical_path_frac": round(min(main_stream_us / wall_inst_us, 1.0), 4) if main_stream_us else None,
                          "device_time_sum_us": dev_sum,
                          "survey_8d_bytes": survey_b, "survey_8d_over_hbm": survey_b / (ms_step * 1e-3) / (HBM_PEAK_GBS * 1e9),
@@ -1264,7 +1284,7 @@ def main():
                        **({"core_switches": args.core} if args.core else {})},
             "roofline": roof,
         }
-        if world == 1 and not args.no_extras and args.rays_per_gpu == CHUNK and args.grid == GRID and args.budget_scale == 1 \
+        if args.full and world == 1 and not args.no_extras and args.rays_per_gpu == CHUNK and args.grid == GRID and args.budget_scale == 1 \
                 and args.table_dtype == "f32":
             del trainer
             # the legs below include host-bound loops (the reference-style loop, the module path): the step batches and the tables of
@@ -1277,7 +1297,7 @@ def main():
             gc.freeze()
             out["extras"] = extras(device, params, focal, main_ms=1e3 * dt_max / args.steps, main_rays=rays_all / args.steps)
             out["psnr_at_iter"] = out["extras"].get("psnr_at_iter")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.cpu_baseline_steps:
                 w_, k_ = (int(v) for v in args.cpu_baseline_steps.split(","))
                 out["cpu_baseline"] = cpu_baseline(budget_s=None, warm=w_, timed=k_)

@@ -72,3 +72,18 @@ def test_dump_outputs_keeps_dtypes_and_the_size_limit(tmp_path):
     assert np.isin(got["bigger"], arrays["bigger"]).all() and np.isin(got["big"], arrays["big"]).all()
     for f in files:
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
+def test_full_is_off_by_default_and_owns_the_cpu_protocol():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` run is the lean one: `--full` (per-kernel table, CPU baseline, extras legs)
+    is off unless asked for, and the CPU baseline's own protocol is refused without it (before any GPU work starts)."""
+    import subprocess
+    import bench
+    ap = bench.arg_parser()
+    plain = ap.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup) == (1, 20, 5)
+    full = ap.parse_args(["--full", "--no-extras"])
+    assert full.full and full.no_extras and not full.no_cpu_baseline
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-baseline-steps", "3,10"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 2 and "--cpu-baseline-steps needs --full" in r.stderr and not r.stdout

@@ -571,6 +571,37 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
         assert np.abs(x - y).max() <= 1e-5 * scale, (k, float(np.abs(x - y).max()), scale)
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_per_kernel_table(tmp_path):
+    """A plain `bench.py` run sets up, warms up, times its steps and prints the line: the roofline of the dominant kernel comes from
+    the timed steps, and there is no per-kernel table, CPU baseline or extras leg.  `--full` (here without its two long legs) adds
+    the per-kernel table of the instrumented steps behind the same line."""
+    import json as _json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NMF_BENCH_SHARE_GPU", "NMF_BENCH_BACKEND"):
+        env.pop(k, None)
+    for full in (False, True):
+        d = tmp_path / ("full" if full else "plain")
+        d.mkdir()
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--detail-dir", str(d)] + (["--full", "--no-extras", "--no-cpu-baseline"] if full else []),
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _json.loads(r.stdout.rstrip().splitlines()[-1])
+        assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert "extras" not in rec and "cpu_baseline" not in rec and "psnr_at_iter" not in rec
+        roof = _json.load(open(d / "bench_detail.json"))["roofline"]
+        assert rec["roofline"]["kernel"] == roof["kernel"] and 0 < roof["frac"] <= 1 and roof["launches"] > 0
+        assert roof["sizes_per_step"]["B"] > 0 and roof["step"]["wall_us"] > 0
+        if full:
+            assert roof["kernel"] in roof["per_kernel"] and roof["step"]["wall_us_instrumented"] > 0
+            assert roof["step"]["device_time_sum_us"] > 0
+        else:
+            assert roof["per_kernel"] is None and roof["step"]["wall_us_instrumented"] is None
+
+
 def test_edge_cases_all_rays_miss_and_single_ray():
     """Rays that never enter the AABB / hit only empty space give M = 0 at level 0; a single ray batch works."""
     from nmf_amd.config import build_model

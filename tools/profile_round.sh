@@ -2,8 +2,8 @@
 # Collect the per-round rocprofv3 evidence on an MI355X box:  tools/profile_round.sh <tag>   (e.g. r01_q)
 # Writes gpurun_out/<tag>_bench.json, <tag>_bench_kernel_stats.csv, <tag>_pmc_{FETCH,WRITE}_SIZE_per_kernel.csv and
 # pmc_vm_bwd.json; copy what is to be judged into profiles/.  PMC passes are separate runs with --kernel-trace only.
-# Optional: BENCH_ARGS="--grid 300" (or "--retrace 1000", "--mode infer --steps 2") profiles another regime: the first, full
-# bench.py run then also takes those arguments (without extras / CPU baseline).
+# Optional: BENCH_ARGS="--grid 300" (or "--retrace 1000", "--mode infer --steps 2") profiles another regime: the first bench.py
+# run (--full: per-kernel table, extras, CPU baseline) then also takes those arguments (without extras / CPU baseline).
 set -u
 TAG=${1:-rXX}
 BENCH_ARGS=${BENCH_ARGS:-}
@@ -13,9 +13,9 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 if [ -n "$BENCH_ARGS" ]; then
-  python "$ROOT/bench.py" $BENCH_ARGS --no-extras --no-cpu-baseline > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+  python "$ROOT/bench.py" --full $BENCH_ARGS --no-extras --no-cpu-baseline > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 else
-  python "$ROOT/bench.py" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+  python "$ROOT/bench.py" --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 fi
 # (the line is the compact one; the per-kernel table and every leg are in the detail file it names)
 cp "$ROOT/bench_detail.json" "$OUT/${TAG}_bench_detail.json" 2>/dev/null
