@@ -1,11 +1,11 @@
-// Host-side fast path for the forward wrappers of nmf_amd/hip.py (compiled with g++, no device code).
+// The per-step wrappers of nmf_amd/hip.py and the fused pass (step_core.inc) in C++ (compiled with g++, no device code).
 //
 // The training step is host-bound where the GPU kernels are short (level-0 shading, the forward tail): a ctypes wrapper
 // costs 10-25 us of Python per call -- one torch.empty per output (~2 us each), a checked data_ptr per argument, ctypes
-// marshalling -- against 3-10 us of kernel time.  The functions here do exactly what the Python wrappers of the same
-// name do (same argument order, same outputs, same checks, same C-ABI entry point of include/nmf_hip.h -- with the
-// compiler checking the prototypes), in ~3 us.  hip.py installs them over its own definitions when this module is
-// present (NMF_HOST_EXT=0 keeps the pure-Python wrappers); nothing else in the package knows about it.
+// marshalling -- against 3-10 us of kernel time.  The functions here are THE implementation of the hip.py wrappers of the
+// same name (output allocation, argument checks, the C-ABI entry point of include/nmf_hip.h -- with the compiler checking
+// the prototypes), in ~3 us.  hip.py loads this module at import and raises without it; each wrapper there is one call into
+// it (a few keep a ctypes path for the argument forms not covered here: bf16 tables, out=None, ...).
 #include <torch/extension.h>
 
 #include <algorithm>

@@ -12,7 +12,7 @@ accumulator, and the conversion of the accumulators into parameter gradients.  I
     the reference's own training loop (train.py:509-747: forward, torch loss, `total_loss.backward()`, `optimizer.step()`).
 
 Scope: is_train=True (or the forward-only evaluation render), the sparse-appearance path (no debug maps), recursion depth
-len(max_retrace_rays) <= 1, the C++ host extension present.  Anything else raises Unsupported BEFORE touching an accumulator and the
+len(max_retrace_rays) <= 1.  Anything else raises Unsupported BEFORE touching an accumulator and the
 caller runs that chunk through the autograd operator graph of nmf_amd/functional.py (tests/test_hip_e2e.py compares the two).
 Replayed bookkeeping of a reference run (noise.Pins on a ReplayNoise: bounce counts, re-trace order, occupancy decisions) is honoured
 by the C++ pass, so the reference's full-size fixtures are checked on THIS path (tests/test_hip_timed_path.py).
@@ -122,9 +122,6 @@ class TrainPass:
         # other, so they can share the streams.
         self._side = _SIDE_STREAMS.setdefault(torch.cuda.current_device() if torch.cuda.is_available() else -1, {})
         self._main = None
-        # the same pass as ONE C++ call per chunk (csrc/step_core.inc, in lib/_nmf_host.so): the methods below stay the
-        # specification and the path for bf16 tables / NMF_STEP_CORE=0 / a missing host extension
-        self._core = None               # context 0's StepCore (None: not created yet, False: no host extension)
         self._ctxs = []                 # chunk contexts: _ns(index, core, main (torch Stream; None = torch's current stream), ...)
         self._ctx_used = []             # contexts with chunks of the running optimizer step in flight
         self._switches = {}
@@ -148,40 +145,30 @@ class TrainPass:
     def supported(self):
         n = self.nerf
         m = n.model
-        return (len(m.max_retrace_rays) <= 1 and n.bg_module is not None and not n.hdr and getattr(m.brdf, "fused", False)
-                and self.core() is not None)
+        return len(m.max_retrace_rays) <= 1 and n.bg_module is not None and not n.hdr and getattr(m.brdf, "fused", False)
 
     # ---- the C++ pass ----------------------------------------------------------------------------------------------
     _CORE_STREAMS = (("mlp", 0), ("mlp", 1), ("env", 0), ("env", 1), ("walk", 1), "sat_bwd", "env_table")
 
     def context(self, i=0):
-        """-> chunk context i (created on first use), or None without the host extension.  Context 0 works on torch's current
-        stream and the process-wide side streams; context i > 0 on a main stream and side streams of its own."""
-        if self._core is False:
-            return None
+        """-> chunk context i (created on first use).  Context 0 works on torch's current stream and the process-wide side
+        streams; context i > 0 on a main stream and side streams of its own."""
         while len(self._ctxs) <= i:
-            fx = hip.HOST_EXT
-            if fx is None or not hasattr(fx, "StepCore"):
-                self._core = False
-                return None
             k = len(self._ctxs)
             main = None
             if k > 0:
                 main = self._side.get(("ctx", k, "main"))
                 if main is None:
                     main = self._side[("ctx", k, "main")] = torch.cuda.Stream()
-            self._ctxs.append(_ns(index=k, core=fx.StepCore(), main=main, key=None, keep=None, static=None, march_blocks=None,
+            self._ctxs.append(_ns(index=k, core=hip.HOST_EXT.StepCore(), main=main, key=None, keep=None, static=None, march_blocks=None,
                                   retrace=None, acc=None, bound=-1))
             for name, v in self._switches.items():
                 setattr(self._ctxs[-1].core, name, v)
-            if k == 0:
-                self._core = self._ctxs[0].core
         return self._ctxs[i]
 
     def core(self, i=0):
-        """-> lib/_nmf_host.so's StepCore of chunk context i, configured for this model, or None (no host extension)"""
-        cx = self.context(i)
-        return None if cx is None else cx.core
+        """-> lib/_nmf_host.so's StepCore of chunk context i, configured for this model"""
+        return self.context(i).core
 
     def cores(self):
         return [cx.core for cx in self._ctxs]
@@ -189,9 +176,9 @@ class TrainPass:
     def set_switch(self, name, value):
         """a boolean switch of the C++ pass (env_split, ...: A/B runs and tests) on every chunk context, present and future"""
         self._switches[name] = value
-        if self.context(0) is not None:
-            for cx in self._ctxs:
-                setattr(cx.core, name, value)
+        self.context(0)
+        for cx in self._ctxs:
+            setattr(cx.core, name, value)
 
     def _param_token(self):
         """(version, storage) of every parameter the derived tables are built from: equal token = equal tables"""
@@ -308,7 +295,7 @@ class TrainPass:
     @torch.no_grad()
     def prefetch(self):
         """Trainer.step calls this after the optimizer step (and the schedule): the next step's derived tables"""
-        if self.core() is None or self._acc_cache is None or not self.supported():
+        if self._acc_cache is None or not self.supported():
             return
         self._core_tables(self._acc_cache.flat.device)
 

@@ -1,13 +1,15 @@
-"""ctypes binding of libnmf_hip.so (include/nmf_hip.h).  This is the ONLY way the host-side operator
-classes reach the GPU kernels; there is no CPU or PyTorch fallback: if the library is missing the
+"""Binding of libnmf_hip.so (include/nmf_hip.h).  This is the ONLY way the host-side operator
+classes reach the GPU kernels; there is no CPU or PyTorch fallback: if a library is missing the
 import of any product operator raises.
 
 torch is used for what it is here for: device memory (tensors), the current HIP stream and
 torch.distributed.  Every wrapper takes torch tensors, checks dtype / contiguity / device and
-passes raw pointers + sizes + the current stream to the C ABI.
+passes raw pointers + sizes + the current stream to the C ABI.  Each wrapper has ONE implementation:
+the per-step ones call lib/_nmf_host.so (csrc/host_ext.cpp: output allocation, checks and the
+C-ABI call in C++, ~3 us per call instead of 10-25 us of Python), the others go through ctypes.
 """
 import ctypes as C
-import math
+import importlib.util
 import os
 
 import numpy as np
@@ -15,6 +17,8 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NMF_HIP_LIB") or os.path.join(_HERE, "lib", "libnmf_hip.so")      # (NMF_HIP_LIB: kernel experiments, tools/)
+HOST_EXT_PATH = os.path.join(_HERE, "lib", "_nmf_host.so")
+_BUILD_HINT = "build it with `python -c 'import __graft_entry__ as g; g.build()'` (or nmf_amd/csrc/build.sh)"
 
 
 class NmfHipError(RuntimeError):
@@ -23,13 +27,30 @@ class NmfHipError(RuntimeError):
 
 def _load():
     if not os.path.exists(LIB_PATH):
-        raise NmfHipError(
-            f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(or nmf_amd/csrc/build.sh).  nmf_amd has no CPU fallback.")
+        raise NmfHipError(f"{LIB_PATH} not found: {_BUILD_HINT}.  nmf_amd has no CPU fallback.")
     return C.CDLL(LIB_PATH)
 
 
+def _load_host():
+    """lib/_nmf_host.so: the C++ wrappers and the fused training / evaluation pass (StepCore).  Required: a missing, broken or
+    stale build raises like a missing libnmf_hip.so does"""
+    if not os.path.exists(HOST_EXT_PATH):
+        raise NmfHipError(f"{HOST_EXT_PATH} not found: {_BUILD_HINT}.  nmf_amd has no CPU fallback.")
+    spec = importlib.util.spec_from_file_location("_nmf_host", HOST_EXT_PATH)
+    mod = importlib.util.module_from_spec(spec)
+    try:
+        spec.loader.exec_module(mod)
+    except ImportError as e:
+        raise NmfHipError(f"{HOST_EXT_PATH} does not load ({e}): {_BUILD_HINT}") from e
+    if mod.abi_version() != _lib.nmf_version():
+        raise NmfHipError(f"{HOST_EXT_PATH} was built against ABI version {mod.abi_version()}, {LIB_PATH} is version "
+                          f"{_lib.nmf_version()}: {_BUILD_HINT}")
+    mod.set_error_class(NmfHipError)
+    return mod
+
+
 _lib = _load()
+HOST_EXT = _load_host()
 
 c_f32p = C.POINTER(C.c_float)
 c_vp = C.c_void_p
@@ -265,38 +286,18 @@ def alpha_coarse(bits, grid):
 
 
 def march_count(p, rays, jitter, alpha_bits, alpha_coarse=None):
-    B = rays.shape[0]
-    W = (p.n_steps + 63) // 64
-    valid = torch.empty((B, W), dtype=torch.int64, device=rays.device)
-    counts = torch.empty(B, dtype=torch.int32, device=rays.device)
-    _check(_lib.nmf_march_count(C.byref(p), _p(rays, torch.float32), C.c_int64(B), _p(jitter), _p(alpha_bits),
-                                _p(alpha_coarse if alpha_bits is not None else None), _p(valid), _p(counts), _stream()),
-           "nmf_march_count")
-    return valid, counts
+    """-> (valid [B, ceil(n_steps / 64)] int64 bit words, counts [B] int32)"""
+    return HOST_EXT.march_count(C.addressof(p), rays, jitter, alpha_bits, alpha_coarse, _stream())
 
 
 def march_scan(counts, max_samples):
-    B = counts.shape[0]
-    offsets = torch.empty(B + 1, dtype=torch.int64, device=counts.device)
-    whole_valid = torch.empty(B, dtype=torch.uint8, device=counts.device)
-    totals = torch.empty(2, dtype=torch.int64, device=counts.device)
-    nbytes = _lib.nmf_march_scan_workspace_bytes(C.c_int64(B))
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=counts.device)
-    _check(_lib.nmf_march_scan(_p(counts, torch.int32), C.c_int64(B), C.c_int64(max_samples), _p(offsets),
-                               _p(whole_valid), _p(totals), _p(ws), C.c_int64(nbytes), _stream()), "nmf_march_scan")
-    return offsets, whole_valid, totals
+    """-> (offsets [B+1] int64, whole_valid [B] uint8, totals [2] int64 = (samples, rays) kept under max_samples)"""
+    return HOST_EXT.march_scan(counts, int(max_samples), _stream())
 
 
 def march_fill(p, rays, b, M, jitter, valid, offsets, want_z=True):
-    dev = rays.device
-    xyzt = torch.empty((M, 4), dtype=torch.float32, device=dev)
-    ray_id = torch.empty(M, dtype=torch.int32, device=dev)
-    step_id = torch.empty(M, dtype=torch.int32, device=dev)
-    z = torch.empty(M, dtype=torch.float32, device=dev) if want_z else None
-    dist = torch.empty(M, dtype=torch.float32, device=dev)
-    _check(_lib.nmf_march_fill(C.byref(p), _p(rays, torch.float32), C.c_int64(b), _p(jitter), _p(valid), _p(offsets),
-                               _p(xyzt), _p(ray_id), _p(step_id), _p(z), _p(dist), _stream()), "nmf_march_fill")
-    return xyzt, ray_id, step_id, z, dist
+    """-> (xyzt [M,4], ray_id [M] int32, step_id [M] int32, z [M] or None, dist [M])"""
+    return HOST_EXT.march_fill(C.addressof(p), rays, b, M, jitter, valid, offsets, want_z, _stream())
 
 
 def march_dense(p, rays, b, jitter, valid):
@@ -337,13 +338,13 @@ def vm_params(aabb, inv_size, density_shift, grid):
 
 def vm_pack_density(p, planes, lines, out=None):
     """planes[i]: [G,G,16] channel-last storage, lines[i]: [G,16].  out = (dpk, dlk) of an earlier call re-packs in place."""
+    if out is not None:
+        HOST_EXT.vm_pack_density_into(C.addressof(p), list(planes), list(lines), list(out[0]), list(out[1]), _stream())
+        return out
     G = p.grid
     dev = planes[0].device
-    if out is not None:
-        dpk, dlk = out
-    else:
-        dpk = [torch.empty((G, G, 48), dtype=torch.float32, device=dev) for _ in range(3)]
-        dlk = [torch.empty((G, 32), dtype=torch.float32, device=dev) for _ in range(3)]
+    dpk = [torch.empty((G, G, 48), dtype=torch.float32, device=dev) for _ in range(3)]
+    dlk = [torch.empty((G, 32), dtype=torch.float32, device=dev) for _ in range(3)]
     _check(_lib.nmf_vm_pack_density(C.byref(p), _p3(planes), _p3(lines), _p3(dpk), _p3(dlk), _stream()),
            "nmf_vm_pack_density")
     return dpk, dlk
@@ -351,6 +352,11 @@ def vm_pack_density(p, planes, lines, out=None):
 
 def vm_query_fwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, want_density=True, want_normal=True,
                  want_app=True, want_coef=False):
+    """-> (sigma_feat [M], sigma [M], grad [M,3], normal [M,3], app [M,24], coef [M,72]); None for what is not asked for"""
+    if app_planes[0].dtype == torch.float32:
+        return HOST_EXT.vm_query_fwd(C.addressof(p), xyzt, dpk, dlk, app_planes, app_lines, basis, want_density, want_normal,
+                                     want_app, want_coef, _stream())
+    # bf16 tables: this ctypes path dispatches on the table dtype
     M = xyzt.shape[0]
     dev = xyzt.device
     f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
@@ -376,32 +382,13 @@ def vm_query_fwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, want_density=T
 
 def vm_query_rows(p, xyzt, dpk, dlk):
     """value + gradient + normal of a few rows (16 lanes per row): -> (sigma_feat [M], grad [M,3], normal [M,3])"""
-    M = xyzt.shape[0]
-    dev = xyzt.device
-    sf = torch.empty(M, dtype=torch.float32, device=dev)
-    gr = torch.empty((M, 3), dtype=torch.float32, device=dev)
-    nr = torch.empty((M, 3), dtype=torch.float32, device=dev)
-    td = dpk[0].dtype
-    _check(_lib.nmf_vm_query_rows(C.byref(p), _p(xyzt, torch.float32), C.c_int64(M), _p3(dpk, td), _p3(dlk, td),
-                                  C.c_int32(1 if td == torch.bfloat16 else 0), _p(sf), None, _p(gr), _p(nr), _stream()),
-           "nmf_vm_query_rows")
-    return sf, gr, nr
+    return HOST_EXT.vm_query_rows(C.addressof(p), xyzt, list(dpk), list(dlk), _stream())
 
 
 def vm_query_sigma(p, xyzt, planes, lines):
     """density value of all samples from the density factors themselves (planes [G,G,16], lines [G,16], fp32 or bfloat16):
     -> (sigma_feat [M], sigma [M]), the bits of vm_query_fwd"""
-    M = xyzt.shape[0]
-    sf = torch.empty(M, dtype=torch.float32, device=xyzt.device)
-    sg = torch.empty(M, dtype=torch.float32, device=xyzt.device)
-    td = planes[0].dtype
-    for t in list(planes) + list(lines):
-        if t.shape[-1] != 16:
-            raise NmfHipError("vm_query_sigma: density factors [G,G,16] / [G,16] expected")
-    _check(_lib.nmf_vm_query_sigma(C.byref(p), _p(xyzt, torch.float32), C.c_int64(M), _p3(planes, td), _p3(lines, td),
-                                   C.c_int32(1 if td == torch.bfloat16 else 0), _p(sf), _p(sg), _stream()),
-           "nmf_vm_query_sigma")
-    return sf, sg
+    return HOST_EXT.vm_query_sigma(C.addressof(p), xyzt, list(planes), list(lines), _stream())
 
 
 def to_bf16_tables(srcs, dsts=None):
@@ -437,11 +424,6 @@ def vm_query_bwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, sigma_feat, gr
                                  _p(g_basis if want_a else None), _p(ws), C.c_int64(nbytes), _stream()), "nmf_vm_query_bwd")
 
 
-class VmBwdSegment(C.Structure):
-    _fields_ = [("xyzt", C.c_void_p), ("M", C.c_int64), ("sigma_feat", C.c_void_p), ("grad", C.c_void_p),
-                ("d_sigma", C.c_void_p), ("d_sigma_feat", C.c_void_p), ("d_normal", C.c_void_p), ("d_app", C.c_void_p)]
-
-
 VM_MAX_SEGMENTS = 4
 
 
@@ -471,58 +453,20 @@ def vm_query_bwd_segments(p, segs, dpk, dlk, app_planes, app_lines, basis, g_dpk
     """One backward walk over several sample sets (no concatenation).  segs: list of tuples
     (xyzt, sigma_feat, grad, d_sigma, d_sigma_feat, d_normal, d_app) -- the argument order of vm_query_bwd.
     plan: vm_bin_plan of the same sample sets (the sort is then not redone).  clean: vm_bwd_clean_scratch (no memset launches)."""
-    n = len(segs)
-    if n > VM_MAX_SEGMENTS:
-        raise NmfHipError(f"at most {VM_MAX_SEGMENTS} segments per walk")
-    arr = (VmBwdSegment * max(n, 1))()
-    M, want_d, want_a = 0, False, False
-    for i, (xyzt, sf, gr, ds, dsf, dn, da) in enumerate(segs):
-        arr[i] = VmBwdSegment(_p(xyzt, torch.float32), xyzt.shape[0], _p(sf), _p(gr), _p(ds), _p(dsf), _p(dn), _p(da))
-        M += xyzt.shape[0]
-        want_d = want_d or ds is not None or dsf is not None or dn is not None
-        want_a = want_a or da is not None
-    if M == 0:
-        return
-    if plan is not None:
-        nbytes = _lib.nmf_vm_walk_workspace_bytes(C.c_int64(M))
-        ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=segs[0][0].device)
-        _check(_lib.nmf_vm_query_bwd_planned(C.byref(p), arr, C.c_int32(n),
-                                             _p3(dpk) if want_d else None, _p3(dlk) if want_d else None,
-                                             _p3(app_planes) if want_a else None, _p3(app_lines) if want_a else None,
-                                             _p(basis) if want_a else None,
-                                             _p3(g_dpk) if want_d else None, _p3(g_dlk) if want_d else None,
-                                             _p3(g_app_planes) if want_a else None, _p3(g_app_lines) if want_a else None,
-                                             _p(g_basis if want_a else None), _p(plan), C.c_int64(plan.numel() * 4), _p(ws),
-                                             C.c_int64(nbytes), _stream()),
-               "nmf_vm_query_bwd_planned")
-        return
-    nbytes = _lib.nmf_vm_bwd_workspace_bytes(C.c_int64(M), C.c_int32(p.grid))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=segs[0][0].device)
+    args = (C.addressof(p), list(segs), dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis)
     if clean is not None:
-        _check(_lib.nmf_vm_query_bwd_segments_clean(C.byref(p), arr, C.c_int32(n),
-                                                    _p3(dpk) if want_d else None, _p3(dlk) if want_d else None,
-                                                    _p3(app_planes) if want_a else None, _p3(app_lines) if want_a else None,
-                                                    _p(basis) if want_a else None,
-                                                    _p3(g_dpk) if want_d else None, _p3(g_dlk) if want_d else None,
-                                                    _p3(g_app_planes) if want_a else None, _p3(g_app_lines) if want_a else None,
-                                                    _p(g_basis if want_a else None), _p(clean), C.c_int64(clean.numel()), _p(ws),
-                                                    C.c_int64(nbytes), _stream()),
-               "nmf_vm_query_bwd_segments_clean")
-        return
-    _check(_lib.nmf_vm_query_bwd_segments(C.byref(p), arr, C.c_int32(n),
-                                          _p3(dpk) if want_d else None, _p3(dlk) if want_d else None,
-                                          _p3(app_planes) if want_a else None, _p3(app_lines) if want_a else None,
-                                          _p(basis) if want_a else None,
-                                          _p3(g_dpk) if want_d else None, _p3(g_dlk) if want_d else None,
-                                          _p3(g_app_planes) if want_a else None, _p3(g_app_lines) if want_a else None,
-                                          _p(g_basis if want_a else None), _p(ws), C.c_int64(nbytes), _stream()),
-           "nmf_vm_query_bwd_segments")
+        return HOST_EXT.vm_query_bwd_clean(*args, clean, _stream())
+    if plan is not None:
+        return HOST_EXT.vm_query_bwd_planned(*args, plan, _stream())
+    return HOST_EXT.vm_query_bwd_segments(*args, _stream())
 
 
 def vm_unpack_density_grad(p, g_dpk, g_dlk, out=None, l1=None):
     """out = (gp, gl) of an earlier call: the same tensors are overwritten (a training pass keeps its gradient tensors).
     l1 = (the six density parameters [planes + lines] in the gradients' storage order, 0-d device scale): the gradient of
     scale * sum_i mean |x_i| is added in the same launch (same bits as l1_mean_bwd(..., out=gp + gl) behind the unpack)"""
+    if out is None and l1 is None:
+        return HOST_EXT.vm_unpack_density_grad(C.addressof(p), g_dpk, g_dlk, _stream())
     G = p.grid
     dev = g_dpk[0].device
     if out is not None:
@@ -551,37 +495,18 @@ def vm_unpack_density_grad(p, g_dpk, g_dlk, out=None, l1=None):
 
 # ---- compositing --------------------------------------------------------------------------------
 def composite_fwd(sigma, dist, offsets, b, distance_scale):
-    M = sigma.shape[0]
-    weight = torch.empty(M, dtype=torch.float32, device=sigma.device)
-    acc = torch.empty(b, dtype=torch.float32, device=sigma.device)
-    if M == 0:                      # no kept sample at all: nothing to launch (empty tensors have no storage)
-        return weight, acc.zero_()
-    _check(_lib.nmf_composite_fwd(_p(sigma, torch.float32), _p(dist, torch.float32), _p(offsets, torch.int64),
-                                  C.c_int64(b), C.c_float(distance_scale), _p(weight), _p(acc), _stream()),
-           "nmf_composite_fwd")
-    return weight, acc
+    """-> (weight [M], acc [b]); M == 0: nothing is launched, acc is zero"""
+    return HOST_EXT.composite_fwd(sigma, dist, offsets, b, distance_scale, _stream())
 
 
 def composite_bwd(sigma, dist, weight, offsets, b, distance_scale, d_weight):
-    d_sigma = torch.empty_like(sigma)
-    if sigma.shape[0] == 0:
-        return d_sigma
-    _check(_lib.nmf_composite_bwd(_p(sigma, torch.float32), _p(dist, torch.float32), _p(weight, torch.float32),
-                                  _p(offsets, torch.int64), C.c_int64(b), C.c_float(distance_scale),
-                                  _p(d_weight.contiguous(), torch.float32), _p(d_sigma), _stream()),
-           "nmf_composite_bwd")
-    return d_sigma
+    """-> d_sigma [M]"""
+    return HOST_EXT.composite_bwd(sigma, dist, weight, offsets, b, distance_scale, d_weight, _stream())
 
 
 def segment_sum(vals, scale, offsets, n_seg, lanes=1):
     """lanes=1: index-order sums (bit-reproducible); lanes=8: eight lanes per segment (tree sum)"""
-    D = vals.shape[1]
-    out = torch.empty((n_seg, D), dtype=torch.float32, device=vals.device)
-    if vals.shape[0] == 0:
-        return out.zero_()
-    _check(_lib.nmf_segment_sum(_p(vals, torch.float32), _p(scale), _p(offsets, torch.int64), C.c_int64(n_seg),
-                                C.c_int32(D), C.c_int32(lanes), _p(out), _stream()), "nmf_segment_sum")
-    return out
+    return HOST_EXT.segment_sum(vals, scale, offsets, n_seg, lanes, _stream())
 
 
 # ---- environment map ---------------------------------------------------------------------------
@@ -590,6 +515,10 @@ def sat_build(bg_mat, brightness=0.0, mul=1.0, sc=None, out=None, pole=False, in
     interleaved copy of sat [H,W,4] with interleaved=True: what the lookups read fastest).  sc: optional device float32 [3] =
     (mipbias, brightness, mul) read by the kernels instead of the by-value scalars (no host read-back of the parameters).
     out = the tuple of an earlier call (same flags) rebuilds the tables in place."""
+    if out is not None and bg_mat.is_contiguous():
+        HOST_EXT.sat_build_into(bg_mat, float(brightness), float(mul), sc, out[0], out[1], out[2] if pole else None,
+                                out[-1] if interleaved else None, _stream())
+        return (out[0], out[1]) + ((out[2],) if pole else ()) + ((out[-1],) if interleaved else ())
     bg = bg_mat.reshape(3, bg_mat.shape[-2], bg_mat.shape[-1])
     H, W = bg.shape[-2:]
     if out is not None:
@@ -615,16 +544,22 @@ def _sat_layout(sat):
 
 def sh_project(vals, wq, sh_A, out=None):
     """-> (coeffs [K,3], conv [K,3]); wq [n,K] contiguous, sh_A [>=K]"""
+    if out is not None:
+        HOST_EXT.sh_project_into(vals, wq, sh_A, out[0], out[1], _stream())
+        return out
     n, K = wq.shape[0], wq.shape[1]
-    if out is None:
-        out = (torch.empty((K, 3), dtype=torch.float32, device=vals.device),
-               torch.empty((K, 3), dtype=torch.float32, device=vals.device))
+    out = (torch.empty((K, 3), dtype=torch.float32, device=vals.device),
+           torch.empty((K, 3), dtype=torch.float32, device=vals.device))
     _check(_lib.nmf_sh_project(_p(vals, torch.float32), _p(wq, torch.float32), C.c_int64(n), C.c_int32(K),
                                _p(sh_A, torch.float32), _p(out[0]), _p(out[1]), _stream()), "nmf_sh_project")
     return out
 
 
 def sat_build_bwd(d_sat, bg_mat, act, d_pole, brightness=0.0, mul=1.0, sc=None, out=None):
+    """-> d_bg [3,H,W] (out: written in place)"""
+    if out is not None and bg_mat.is_contiguous():
+        HOST_EXT.sat_build_bwd_into(d_sat, bg_mat, act, d_pole, float(brightness), float(mul), sc, out, _stream())
+        return out
     bg = bg_mat.reshape(3, bg_mat.shape[-2], bg_mat.shape[-1])
     H, W = bg.shape[-2:]
     d_bg = out if out is not None else torch.empty_like(bg)
@@ -637,13 +572,7 @@ def sat_build_bwd(d_sat, bg_mat, act, d_pole, brightness=0.0, mul=1.0, sc=None, 
 def sat_lookup_fwd(sat, dirs, sa, mipbias, pole_rows, sc=None):
     """dirs: [R,3] directions, or [R,6] ray rows (origin | direction) looked up along their columns 3..5; sat: the planar
     table [3,H,W] or sat_build's interleaved copy [H,W,4] (same results)"""
-    R, ld = dirs.shape[0], dirs.shape[1]
-    H, W, layout = _sat_layout(sat)
-    out = torch.empty((R, 3), dtype=torch.float32, device=dirs.device)
-    _check(_lib.nmf_sat_lookup_fwd(_p(sat, torch.float32), C.c_int32(H), C.c_int32(W), _p(dirs, torch.float32),
-                                   C.c_int32(ld), _p(sa, torch.float32), C.c_int64(R), C.c_float(mipbias), _p(sc), _p(pole_rows),
-                                   C.c_int32(layout), _p(out), _stream()), "nmf_sat_lookup_fwd")
-    return out
+    return HOST_EXT.sat_lookup_fwd(sat, dirs, sa, mipbias, pole_rows, sc, _stream())
 
 
 # lookups per call from which the table adjoint is binned (three more launches than the direct scatter; measured with
@@ -663,11 +592,14 @@ def _cdiv(a, b):
 def sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, want_dirs=True, want_mipbias=None, sc=None):
     """d_sat [H,W,4] / d_pole [2,3] / d_mip [1] are ACCUMULATED into (any may be None except d_pole).  Returns d_dirs; with
     want_mipbias=True (legacy form) a fresh d_mip accumulator is allocated and (d_dirs, d_mip) is returned."""
+    if want_mipbias is None:
+        return HOST_EXT.sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, sc,
+                                       int(ENV_BINNED_MIN_LOOKUPS), _stream())
+    # the legacy return form (tests)
     R, ld = dirs.shape[0], dirs.shape[1]
     H, W, layout = _sat_layout(sat)
     d_dirs = torch.empty((R, ld), dtype=torch.float32, device=dirs.device) if want_dirs else None   # shaped like dirs
-    legacy = want_mipbias is not None
-    if legacy and want_mipbias and d_mip is None:
+    if want_mipbias and d_mip is None:
         d_mip = torch.zeros(1, dtype=torch.float32, device=dirs.device)
     if d_sat is not None and R >= ENV_BINNED_MIN_LOOKUPS and _cdiv(H, 32) * _cdiv(W, 64) <= 1024:
         # many lookups: the binned table adjoint (csrc/env.hip).  The record pool comes from torch's stream-ordered caching
@@ -679,25 +611,19 @@ def sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, wan
                                               C.c_int32(layout), _p(d_out.contiguous(), torch.float32), _p(d_sat), _p(d_pole),
                                               _p(d_dirs), _p(d_mip), _p(ws), C.c_int64(nbytes), _stream()),
                "nmf_sat_lookup_bwd_binned")
-        return (d_dirs, d_mip) if legacy else d_dirs
+        return d_dirs, d_mip
     _check(_lib.nmf_sat_lookup_bwd(_p(sat, torch.float32), C.c_int32(H), C.c_int32(W), _p(dirs, torch.float32),
                                    C.c_int32(ld), _p(sa, torch.float32), C.c_int64(R), C.c_float(mipbias), _p(sc), C.c_int32(layout),
                                    _p(d_out.contiguous(), torch.float32), _p(d_sat), _p(d_pole), _p(d_dirs), _p(d_mip),
                                    _stream()), "nmf_sat_lookup_bwd")
-    return (d_dirs, d_mip) if legacy else d_dirs
+    return d_dirs, d_mip
 
 
 # ---- shading helpers -------------------------------------------------------------------------------
 def select_bounces(weights, u, mode, mul, add=0.0, sum_w=1.0):
     """sum_w: python float, or a 0-d fp32 DEVICE tensor (read by the kernel: no host sync)."""
-    M = weights.shape[0]
-    counts = torch.empty(M, dtype=torch.int32, device=weights.device)
     dev_sum = sum_w if isinstance(sum_w, torch.Tensor) else None
-    _check(_lib.nmf_select_bounces(_p(weights, torch.float32), _p(u, torch.float32), C.c_int64(M), C.c_int32(mode),
-                                   C.c_float(mul), C.c_float(add), C.c_float(1.0 if dev_sum is not None else sum_w),
-                                   _p(dev_sum, torch.float32), _p(counts), _stream()),
-           "nmf_select_bounces")
-    return counts
+    return HOST_EXT.select_bounces(weights, u, mode, mul, add, 1.0 if dev_sum is not None else sum_w, dev_sum, _stream())
 
 
 _select_ws = {}
@@ -715,68 +641,37 @@ def select_total_workspace(dev, stream=None):
 
 def select_total(weights, u, extra):
     """-> 0-d fp32 device tensor clip(float(sum(w) + 1e-3 * (sum(u) + extra)), 1e-3) (one launch, float64 sums)"""
-    dev = weights.device
-    ws = select_total_workspace(dev)
-    total = torch.empty((), dtype=torch.float32, device=dev)
-    _check(_lib.nmf_select_total(_p(weights, torch.float32), _p(u, torch.float32), C.c_int64(weights.shape[0]),
-                                 C.c_double(float(extra)), _p(ws), _p(total), _stream()), "nmf_select_total")
-    return total
+    return HOST_EXT.select_total(weights, u, float(extra), select_total_workspace(weights.device), _stream())
 
 
 def view_adjoint_to_rays(ray_id, bidx, dv_a, dv_b, d_rays):
     """d_rays [B,6] (columns 3..5) -= per-row view adjoints dv_a [Mb,>=3] (+ dv_b), rows may be column slices"""
-    Mb = bidx.shape[0]
-    (pa, la) = _rows(dv_a, 3)
-    (pb, lb) = _rows(dv_b, 3) if dv_b is not None else (None, 3)
-    _check(_lib.nmf_view_adjoint_to_rays(_p(ray_id, torch.int32), _p(bidx, torch.int32), pa, C.c_int32(la), pb, C.c_int32(lb),
-                                         C.c_int64(Mb), _p(d_rays, torch.float32), _stream()), "nmf_view_adjoint_to_rays")
+    return HOST_EXT.view_adjoint_to_rays(ray_id, bidx, dv_a, dv_b, d_rays, _stream())
 
 
 def expand_segments(offsets, n_seg, total):
-    seg = torch.empty(total, dtype=torch.int32, device=offsets.device)
-    loc = torch.empty(total, dtype=torch.int32, device=offsets.device)
-    _check(_lib.nmf_expand_segments(_p(offsets, torch.int64), C.c_int64(n_seg), _p(seg), _p(loc), _stream()),
-           "nmf_expand_segments")
-    return seg, loc
+    """-> (seg [total] int32 = the segment of each element, loc [total] int32 = its index inside the segment)"""
+    return HOST_EXT.expand_segments(offsets, n_seg, total, _stream())
 
 
 def segment_sum_wide(vals, D, offsets, n_seg):
-    out = torch.empty((n_seg, D), dtype=torch.float32, device=vals.device)
-    if vals.shape[0] == 0:
-        return out.zero_()
-    _check(_lib.nmf_segment_sum_wide(_p(vals, torch.float32), C.c_int64(vals.shape[1]), C.c_int32(D),
-                                     _p(offsets, torch.int64), C.c_int64(n_seg), _p(out), _stream()),
-           "nmf_segment_sum_wide")
-    return out
+    """-> [n_seg, D]: per-segment sums of the first D columns of vals"""
+    return HOST_EXT.segment_sum_wide(vals, D, offsets, n_seg, _stream())
 
 
 def brdf_mlp_pack(weights, into=None):
     """The six weight tensors as the packed image the fused MLP kernels copy into LDS (nmf_brdf_mlp_pack): built once per weight
     update, passed as `image=` to brdf_mlp_fwd / brdf_mlp_bwd.  into: a uint8 device tensor of nmf_brdf_mlp_image_bytes() to reuse."""
-    n = int(_lib.nmf_brdf_mlp_image_bytes())
-    img = into if into is not None else torch.empty(n, dtype=torch.uint8, device=weights[0].device)
-    if img.dtype != torch.uint8 or not img.is_contiguous() or img.numel() < n:
-        raise ValueError("brdf_mlp_pack: `into` must be a contiguous uint8 tensor of nmf_brdf_mlp_image_bytes() bytes")
-    _check(_lib.nmf_brdf_mlp_pack(*[_p(w, torch.float32) for w in weights], _p(img), C.c_int64(img.numel()), _stream()),
-           "nmf_brdf_mlp_pack")
-    return img
+    return HOST_EXT.brdf_mlp_pack(list(weights), into, _stream())
 
 
 def brdf_mlp_fwd(weights, half_vec, diff_vec, feat_src, rough_src, src_idx, out_bias, max_workgroups=0, with_mask=False, image=None):
     """weights = (W0 [64,66], b0, W2 [64,64], b2, W4 [4,64], b4); max_workgroups: see brdf_mlp_bwd.  with_mask: also return
     the ReLU masks [R, 4] (int32 storage) that brdf_mlp_bwd takes together with the output.  image: brdf_mlp_pack(weights) --
     the same bits, a shorter launch (`weights` is then not read)."""
-    R = half_vec.shape[0]
-    out = torch.empty((R, 3), dtype=torch.float32, device=half_vec.device)
-    mask = torch.empty((R, 4), dtype=torch.int32, device=half_vec.device) if with_mask else None
-    tail = (_p(half_vec, torch.float32), _p(diff_vec, torch.float32), _p(feat_src, torch.float32), _p(rough_src, torch.float32),
-            _p(src_idx, torch.int32), C.c_int64(R), C.c_float(out_bias), _p(out), _p(mask, torch.int32), C.c_int32(max_workgroups),
-            _stream())
-    if image is not None:
-        _check(_lib.nmf_brdf_mlp_fwd_packed(_p(image), *tail), "nmf_brdf_mlp_fwd_packed")
-    else:
-        _check(_lib.nmf_brdf_mlp_fwd(*[_p(w, torch.float32) for w in weights], *tail), "nmf_brdf_mlp_fwd")
-    return (out, mask) if with_mask else out
+    r = HOST_EXT.brdf_mlp_fwd(list(weights or ()), half_vec, diff_vec, feat_src, rough_src, src_idx, out_bias, bool(with_mask),
+                              int(max_workgroups), _stream(), image)
+    return r if with_mask else r[0]
 
 
 def brdf_mlp_bwd(weights, half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_out, act_mask, d_out, grads, max_workgroups=0,
@@ -785,20 +680,8 @@ def brdf_mlp_bwd(weights, half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_
     shaped like `weights`, ACCUMULATED into (caller zeroes them once per pass).  max_workgroups > 0 caps the persistent
     workgroups (a launch that shares the chip with kernels of another stream).  -> d_feat [rows of feat_src, 24]: the adjoint of
     feat_src, summed over the rays that gathered each row (src_idx must be non-decreasing)."""
-    R = half_vec.shape[0]
-    dev = half_vec.device
-    d_feat = torch.zeros((feat_src.shape[0], 24), dtype=torch.float32, device=dev)
-    nws = int(_lib.nmf_brdf_mlp_bwd_workspace_bytes(C.c_int64(R), C.c_int32(max_workgroups)))
-    ws = torch.empty(max(nws, 4) // 4, dtype=torch.float32, device=dev)
-    tail = (_p(half_vec, torch.float32), _p(diff_vec, torch.float32), _p(feat_src, torch.float32), _p(rough_src, torch.float32),
-            _p(src_idx, torch.int32), C.c_int64(R), _p(fwd_out, torch.float32), _p(act_mask, torch.int32),
-            _p(d_out.contiguous(), torch.float32), _p(d_feat), *[_p(g) for g in grads], C.c_int32(max_workgroups), _p(ws),
-            C.c_int64(nws), _stream())
-    if image is not None:
-        _check(_lib.nmf_brdf_mlp_bwd_packed(_p(image), *tail), "nmf_brdf_mlp_bwd_packed")
-    else:
-        _check(_lib.nmf_brdf_mlp_bwd(*[_p(w, torch.float32) for w in weights], *tail), "nmf_brdf_mlp_bwd")
-    return d_feat
+    return HOST_EXT.brdf_mlp_bwd(list(weights or ()), half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_out, act_mask, d_out,
+                                 list(grads), int(max_workgroups), _stream(), image)
 
 
 class MlpBwdSegment(C.Structure):
@@ -835,37 +718,18 @@ def brdf_mlp_bwd_segments(weights, sets, grads, max_workgroups=0, image=None):
 
 def heads_fwd(feat, W, b, hp):
     """hp = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)"""
-    M = feat.shape[0]
-    out = torch.empty((M, 11), dtype=torch.float32, device=feat.device)
-    _check(_lib.nmf_heads_fwd(_p(feat, torch.float32), C.c_int64(M), _p(W, torch.float32), _p(b, torch.float32),
-                              *[C.c_float(v) for v in hp], _p(out), _stream()), "nmf_heads_fwd")
-    return out
+    return HOST_EXT.heads_fwd(feat, W, b, list(hp), _stream())
 
 
 def heads_bwd(feat, W, b, hp, d_out, gW, gb, add_into=None):
     """gW [11,24] / gb [11] are ACCUMULATED into.  add_into: another adjoint of the same rows (dense fp32 [M,24]); the result is
     added to it in place and it is returned (one launch less than `add_into += heads_bwd(...)`, the same bits)."""
-    M = feat.shape[0]
-    if add_into is not None and (add_into.dtype != torch.float32 or not add_into.is_contiguous() or add_into.numel() != feat.numel()):
-        raise ValueError("heads_bwd: add_into must be a dense float32 [M,24] tensor")
-    d_feat = torch.empty_like(feat) if add_into is None else add_into
-    _check(_lib.nmf_heads_bwd(_p(feat, torch.float32), C.c_int64(M), _p(W, torch.float32), _p(b, torch.float32),
-                              *[C.c_float(v) for v in hp], _p(d_out.contiguous(), torch.float32),
-                              None if add_into is None else _p(add_into, torch.float32), _p(d_feat), _p(gW),
-                              _p(gb), _stream()), "nmf_heads_bwd")
-    return d_feat
+    return HOST_EXT.heads_bwd(feat, W, b, list(hp), d_out, gW, gb, add_into, _stream())
 
 
 def ggx_rays_fwd(V, N, r, x, off, cnt, sobol, row_of_ray, j_of_ray):
-    R = row_of_ray.shape[0]
-    dev = V.device
-    f = lambda *s_: torch.empty(s_, dtype=torch.float32, device=dev)  # noqa: E731
-    L, hl, dl, lpdf, mip, rays = f(R, 3), f(R, 3), f(R, 3), f(R), f(R), f(R, 6)
-    _check(_lib.nmf_ggx_rays_fwd(_p(V, torch.float32), _p(N, torch.float32), _p(r, torch.float32), _p(x, torch.float32),
-                                 _p(off, torch.float32), _p(cnt, torch.int32), _p(sobol, torch.float32),
-                                 _p(row_of_ray, torch.int32), _p(j_of_ray, torch.int32), C.c_int64(R), _p(L), _p(hl),
-                                 _p(dl), _p(lpdf), _p(mip), _p(rays), _stream()), "nmf_ggx_rays_fwd")
-    return L, hl, dl, lpdf, mip, rays
+    """-> (L [R,3], half [R,3], diff [R,3], lpdf [R], mip [R], rays [R,6])"""
+    return HOST_EXT.ggx_rays_fwd(V, N, r, x, off, cnt, sobol, row_of_ray, j_of_ray, _stream())
 
 
 def ggx_prob(dir_in, dir_out, half, rough):
@@ -877,65 +741,35 @@ def ggx_prob(dir_in, dir_out, half, rough):
 
 
 def ggx_rays_bwd(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays=None):
-    R = row_of_ray.shape[0]
-    d_nr = torch.empty((R, 4), dtype=torch.float32, device=V.device)
-    _check(_lib.nmf_ggx_rays_bwd(_p(V, torch.float32), _p(N, torch.float32), _p(r, torch.float32), _p(off, torch.float32),
-                                 _p(sobol, torch.float32), _p(row_of_ray, torch.int32), _p(j_of_ray, torch.int32),
-                                 C.c_int64(R), _p(dL), _p(d_rays), _p(d_nr), _stream()), "nmf_ggx_rays_bwd")
-    return d_nr
+    """-> d_nr [R,4] = per-ray adjoints of (normal | roughness)"""
+    return HOST_EXT.ggx_rays_bwd(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays, _stream())
 
 
 def ggx_rays_bwd_view(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays=None):
     """-> d_nrv [R,7] = per-ray adjoints of (normal | roughness | view direction)"""
-    R = row_of_ray.shape[0]
-    d = torch.empty((R, 7), dtype=torch.float32, device=V.device)
-    _check(_lib.nmf_ggx_rays_bwd_view(_p(V, torch.float32), _p(N, torch.float32), _p(r, torch.float32), _p(off, torch.float32),
-                                      _p(sobol, torch.float32), _p(row_of_ray, torch.int32), _p(j_of_ray, torch.int32),
-                                      C.c_int64(R), _p(dL), _p(d_rays), _p(d), _stream()), "nmf_ggx_rays_bwd_view")
-    return d
+    return HOST_EXT.ggx_rays_bwd_view(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays, _stream())
 
 
 def shade_mix_bwd_view(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows):
     """shade_mix_bwd plus dV [R,3]"""
-    R = row_of_ray.shape[0]
-    dev = V.device
-    f = lambda *s_: torch.empty(s_, dtype=torch.float32, device=dev)  # noqa: E731
-    d_inc, d_brdf, dL, d_fd, dV = f(R, 3), f(R, 3), f(R, 3), f(R, 6), f(R, 3)
-    _check(_lib.nmf_shade_mix_bwd_view(_p(V, torch.float32), _p(f0, torch.float32), _p(diff, torch.float32),
-                                       _p(cnt, torch.int32), _p(row_of_ray, torch.int32), C.c_int64(R), _p(L, torch.float32),
-                                       _p(inc, torch.float32), _p(brdf, torch.float32), _p(d_rows, torch.float32), _p(d_inc),
-                                       _p(d_brdf), _p(dL), _p(d_fd), _p(dV), _stream()), "nmf_shade_mix_bwd_view")
-    return d_inc, d_brdf, dL, d_fd, dV
+    return HOST_EXT.shade_mix_bwd_view(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows, _stream())
 
 
 def shade_mix_fwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf):
-    R = row_of_ray.shape[0]
-    contrib = torch.empty((R, 3), dtype=torch.float32, device=V.device)
-    _check(_lib.nmf_shade_mix_fwd(_p(V, torch.float32), _p(f0, torch.float32), _p(diff, torch.float32), _p(cnt, torch.int32),
-                                  _p(row_of_ray, torch.int32), C.c_int64(R), _p(L, torch.float32), _p(inc, torch.float32),
-                                  _p(brdf, torch.float32), _p(contrib), _stream()), "nmf_shade_mix_fwd")
-    return contrib
+    """-> contrib [R,3]"""
+    return HOST_EXT.shade_mix_fwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, _stream())
 
 
 def shade_mix_bwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows):
-    R = row_of_ray.shape[0]
-    dev = V.device
-    d_inc = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    d_brdf = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    dL = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    d_fd = torch.empty((R, 6), dtype=torch.float32, device=dev)
-    _check(_lib.nmf_shade_mix_bwd(_p(V, torch.float32), _p(f0, torch.float32), _p(diff, torch.float32), _p(cnt, torch.int32),
-                                  _p(row_of_ray, torch.int32), C.c_int64(R), _p(L, torch.float32), _p(inc, torch.float32),
-                                  _p(brdf, torch.float32), _p(d_rows, torch.float32), _p(d_inc), _p(d_brdf), _p(dL),
-                                  _p(d_fd), _stream()), "nmf_shade_mix_bwd")
-    return d_inc, d_brdf, dL, d_fd
+    """-> (d_inc [R,3], d_brdf [R,3], dL [R,3], d_fd [R,6])"""
+    return HOST_EXT.shade_mix_bwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows, _stream())
 
 
 # ---- optimizer ----------------------------------------------------------------------------------
 def adam_step(slots, n, guard=None):
     """slots: (AdamSlot * k) host array, the first n entries are applied in one launch (nmf_adam_step); guard: optional 0-d fp32
     device tensor, a non-finite value turns the launch into a no-op"""
-    _check(_lib.nmf_adam_step_guarded(slots, C.c_int32(n), _p(guard, torch.float32), _stream()), "nmf_adam_step")
+    return HOST_EXT.adam_step(C.addressof(slots), int(n), guard, _stream())
 
 
 # ---- shading glue --------------------------------------------------------------------------------
@@ -943,22 +777,7 @@ def bounce_index(counts, xyzt=None):
     """counts [M] int32 -> (bidx [M] int32, row_off [M+1] int64, cnt_rows [M] int32, inv [M] int32,
     totals [2] int64 = (R, Mb)); the caller slices bidx[:Mb] / row_off[:Mb+1] / cnt_rows[:Mb] once it has read totals.
     With xyzt [M,4]: a sixth output xyzt_rows [M,4] whose first Mb rows are xyzt[bidx]."""
-    M = counts.shape[0]
-    dev = counts.device
-    rows = torch.empty((max(M, 1), 4), dtype=torch.float32, device=dev) if xyzt is not None else None
-    bidx = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    row_off = torch.empty(M + 1, dtype=torch.int64, device=dev)
-    inv = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    cnt_rows = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    totals = torch.empty(2, dtype=torch.int64, device=dev)
-    nbytes = _lib.nmf_bounce_index_workspace_bytes(C.c_int64(M))
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    _check(_lib.nmf_bounce_index(_p(counts, torch.int32) if M else C.c_void_p(0), C.c_int64(M), _p(bidx), _p(row_off),
-                                 _p(cnt_rows), _p(inv), _p(totals), _p(xyzt, torch.float32) if (xyzt is not None and M) else None,
-                                 _p(rows), _p(ws), C.c_int64(nbytes), _stream()), "nmf_bounce_index")
-    if xyzt is not None:
-        return bidx, row_off, cnt_rows, inv[:M], totals, rows
-    return bidx, row_off, cnt_rows, inv[:M], totals
+    return HOST_EXT.bounce_index(counts, xyzt, _stream())
 
 
 def bounce_prep_fwd_heads(bidx, normals, app, head_W, head_b, hp, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough, row_inputs=1):
@@ -1002,86 +821,30 @@ def bounce_index_select(weights, u, mode, mul, add=0.0, sum_w=1.0, xyzt=None):
 
 
 def bounce_prep_fwd(bidx, normals, app, heads, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough, row_inputs=False):
-    Mb = bidx.shape[0]
-    dev = normals.device
-    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
-    V, N, r1, f0, diff, feat, xyz = f(Mb, 3), f(Mb, 3), f(Mb), f(Mb, 3), f(Mb, 3), f(Mb, 24), f(Mb, 3)
-    if Mb:
-        _check(_lib.nmf_bounce_prep_fwd(_p(bidx, torch.int32), C.c_int64(Mb), _p(normals, torch.float32),
-                                        _p(app, torch.float32), _p(heads, torch.float32), _p(xyzt, torch.float32),
-                                        _p(ray_id, torch.int32), _p(rays, torch.float32), _p(conv, torch.float32),
-                                        _p(feat_noise), C.c_float(anoise), C.c_float(min_rough), C.c_int32(int(row_inputs)),
-                                        _p(V), _p(N), _p(r1),
-                                        _p(f0), _p(diff), _p(feat), _p(xyz), _stream()), "nmf_bounce_prep_fwd")
-    return V, N, r1, f0, diff, feat, xyz
-
-
-def _rows(t, width):
-    """(pointer, row pitch in floats) of a [n,width] / [n] fp32 tensor whose rows are dense but may be a column slice of
-    a wider tensor; anything else is made contiguous first."""
-    if t is None:
-        return C.c_void_p(0), width
-    if t.dtype != torch.float32 or not t.is_cuda:
-        raise NmfHipError("expected a float32 device tensor")
-    ok = (t.dim() == 2 and t.shape[1] == width and t.stride(1) == 1) or (t.dim() == 1 and width == 1)
-    if not ok or t.stride(0) < width:
-        t = t.contiguous()
-    return C.c_void_p(t.data_ptr()), (t.stride(0) if t.shape[0] > 1 else width)
+    """-> (V [Mb,3], N [Mb,3], r1 [Mb], f0 [Mb,3], diffuse [Mb,3], feat [Mb,24], xyz [Mb,3])"""
+    return HOST_EXT.bounce_prep_fwd(bidx, normals, app, heads, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough,
+                                    int(row_inputs), _stream())
 
 
 def bounce_prep_bwd(inv, normals, heads, ray_id, rays, conv, min_rough, detach_n, dN, dr1, df0, ddiff, dfeat,
                     bidx=None, row_inputs=False):
     """row_inputs: heads is [Mb,11] and d_heads / d_app come back per bounce row ([Mb,11], [Mb,24]); row_inputs == 2: normals
     [Mb,3] and d_normals [Mb,3] are per bounce row too (inv may be None, M is taken from ray_id)"""
-    M = inv.shape[0] if inv is not None else ray_id.shape[0]
-    Mb = bidx.shape[0] if bidx is not None else 0
-    n_out = Mb if row_inputs else M
-    dev = normals.device
-    d_normals = torch.empty((Mb if int(row_inputs) == 2 else M, 3), dtype=torch.float32, device=dev)
-    d_heads = torch.empty((n_out, 11), dtype=torch.float32, device=dev)
-    d_app = torch.empty((n_out, 24), dtype=torch.float32, device=dev)
-    if M:
-        (pN, sN), (pr, sr), (pf, sf), (pd, sd) = _rows(dN, 3), _rows(dr1, 1), _rows(df0, 3), _rows(ddiff, 3)
-        strides = (C.c_int32 * 4)(sN, sr, sf, sd)
-        _check(_lib.nmf_bounce_prep_bwd(_p(inv, torch.int32) if inv is not None else None, C.c_int64(M), _p(bidx), C.c_int64(Mb),
-                                        _p(normals, torch.float32), _p(heads if heads.shape[0] else None),
-                                        _p(ray_id, torch.int32), _p(rays, torch.float32), _p(conv, torch.float32),
-                                        C.c_float(min_rough), C.c_int32(1 if detach_n else 0),
-                                        C.c_int32(int(row_inputs)), pN, pr, pf, pd, strides, _p(dfeat), _p(d_normals), _p(d_heads), _p(d_app),
-                                        _stream()), "nmf_bounce_prep_bwd")
-    return d_normals, d_heads, d_app
+    return HOST_EXT.bounce_prep_bwd(inv, normals, heads, ray_id, rays, conv, float(min_rough), bool(detach_n), dN, dr1, df0, ddiff,
+                                    dfeat, bidx, int(row_inputs), _stream())
 
 
 def ray_compose_fwd(weight, refl_rows, inv, normals, rays, offsets, B, bg, bg_per_ray, tonemap, noclip, want_ori):
-    dev = weight.device
-    rgb_map = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    acc = torch.empty(B, dtype=torch.float32, device=dev)
-    rgb_lin = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    ori = torch.empty(B, dtype=torch.float32, device=dev) if want_ori else None
-    if B:
-        _check(_lib.nmf_ray_compose_fwd(_p(weight, torch.float32), _p(refl_rows), _p(inv), _p(normals),
-                                        _p(rays, torch.float32), _p(offsets, torch.int64), C.c_int64(B),
-                                        _p(bg, torch.float32), C.c_int32(1 if bg_per_ray else 0),
-                                        C.c_int32(1 if tonemap else 0), C.c_int32(1 if noclip else 0), _p(rgb_map),
-                                        _p(acc), _p(rgb_lin), _p(ori), _stream()), "nmf_ray_compose_fwd")
-    return rgb_map, acc, rgb_lin, ori
+    """-> (rgb_map [B,3], acc [B], rgb_lin [B,3], ori [B] or None)"""
+    return HOST_EXT.ray_compose_fwd(weight, refl_rows, inv, normals, rays, offsets, B, bg, bool(bg_per_ray), bool(tonemap),
+                                    bool(noclip), bool(want_ori), _stream())
 
 
 def ray_compose_bwd(weight, refl_rows, inv, normals, rays, ray_id, bg, bg_per_ray, tonemap, noclip, rgb_lin, d_rgb_map,
                     d_acc, d_ori, want_d_normals):
-    M = weight.shape[0]
-    dev = weight.device
-    d_weight = torch.empty(M, dtype=torch.float32, device=dev)
-    d_refl = torch.empty_like(refl_rows) if refl_rows is not None else None
-    d_normals = torch.empty((M, 3), dtype=torch.float32, device=dev) if want_d_normals else None
-    if M:
-        _check(_lib.nmf_ray_compose_bwd(_p(weight, torch.float32), _p(refl_rows), _p(inv), _p(normals),
-                                        _p(rays, torch.float32), _p(ray_id, torch.int32), C.c_int64(M),
-                                        _p(bg, torch.float32), C.c_int32(1 if bg_per_ray else 0),
-                                        C.c_int32(1 if tonemap else 0), C.c_int32(1 if noclip else 0), _p(rgb_lin),
-                                        _p(d_rgb_map), _p(d_acc), _p(d_ori), _p(d_weight), _p(d_refl), _p(d_normals),
-                                        _stream()), "nmf_ray_compose_bwd")
-    return d_weight, d_refl, d_normals
+    """-> (d_weight [M], d_refl shaped like refl_rows or None, d_normals [M,3] or None)"""
+    return HOST_EXT.ray_compose_bwd(weight, refl_rows, inv, normals, rays, ray_id, bg, bool(bg_per_ray), bool(tonemap),
+                                    bool(noclip), rgb_lin, d_rgb_map, d_acc, d_ori, bool(want_d_normals), _stream())
 
 
 # ---- loss terms ------------------------------------------------------------------------------------
@@ -1104,16 +867,16 @@ def l1_mean_fwd(tensors):
 
 def l1_mean_bwd(tensors, d_out, out=None):
     """-> gradients in the tensors' own memory order; out = existing gradient tensors of the same storage order to ADD into"""
+    if out is not None:
+        HOST_EXT.l1_mean_bwd_into(list(tensors), d_out, list(out), _stream())
+        return out
     n = len(tensors)
-    grads = out if out is not None else [torch.empty_like(t, memory_format=torch.preserve_format) for t in tensors]
+    grads = [torch.empty_like(t, memory_format=torch.preserve_format) for t in tensors]
     ptrs = (C.c_void_p * n)(*[_dense_f32(t) for t in tensors])
     gptrs = (C.c_void_p * n)(*[_dense_f32(g) for g in grads])
     numel = (C.c_int64 * n)(*[t.numel() for t in tensors])
-    for t, g in zip(tensors, grads):
-        if g.numel() != t.numel():
-            raise NmfHipError("l1_mean_bwd: gradient / tensor size mismatch")
-    _check(_lib.nmf_l1_mean_bwd(ptrs, numel, C.c_int32(n), _p(d_out, torch.float32), gptrs, C.c_int32(0 if out is None else 1),
-                                _stream()), "nmf_l1_mean_bwd")
+    _check(_lib.nmf_l1_mean_bwd(ptrs, numel, C.c_int32(n), _p(d_out, torch.float32), gptrs, C.c_int32(0), _stream()),
+           "nmf_l1_mean_bwd")
     return grads
 
 
@@ -1130,14 +893,7 @@ def loss_mix_fwd(tensors, weights, scale):
 
 def loss_mix_bwd(shapes, weights, scale, d_out):
     """constant gradients d_out * scale * w_i shaped like the inputs (one launch)"""
-    n = len(shapes)
-    grads = [torch.empty(s, dtype=torch.float32, device=d_out.device) for s in shapes]
-    numel = (C.c_int64 * n)(*[g.numel() for g in grads])
-    w = (C.c_float * n)(*[float(v) for v in weights])
-    gptrs = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
-    _check(_lib.nmf_loss_mix_bwd(numel, w, C.c_int32(n), C.c_float(scale), _p(d_out, torch.float32), gptrs, _stream()),
-           "nmf_loss_mix_bwd")
-    return grads
+    return HOST_EXT.loss_mix_bwd([list(s_) for s_ in shapes], [float(v) for v in weights], float(scale), d_out, _stream())
 
 
 _loss_ws = {}
@@ -1179,19 +935,13 @@ def bg_adjoint(acc, d_rgb):
 
 
 def sqerr_fwd(pred, gt):
-    out = torch.zeros((), dtype=torch.float32, device=pred.device)
-    if pred.numel():
-        _check(_lib.nmf_sqerr_fwd(_p(pred, torch.float32), _p(gt, torch.float32), C.c_int64(pred.numel()), _p(out),
-                                  _stream()), "nmf_sqerr_fwd")
-    return out
+    """-> 0-d sum (clip(pred, 0, 1) - clip(gt, 0, 1))^2 (the photometric term)"""
+    return HOST_EXT.sqerr_fwd(pred, gt, _stream())
 
 
 def sqerr_bwd(pred, gt, d_out):
-    d_pred = torch.empty_like(pred)
-    if pred.numel():
-        _check(_lib.nmf_sqerr_bwd(_p(pred, torch.float32), _p(gt, torch.float32), C.c_int64(pred.numel()),
-                                  _p(d_out, torch.float32), _p(d_pred), _stream()), "nmf_sqerr_bwd")
-    return d_pred
+    """-> d_pred = 2 (pred - clip(gt)) d_out inside [0, 1], 0 outside (d_out: 0-d device tensor)"""
+    return HOST_EXT.sqerr_bwd(pred, gt, d_out, _stream())
 
 
 # ---- retrace selection ------------------------------------------------------------------------------
@@ -1235,7 +985,7 @@ def topk_select(keys, k):
 
 def multi_copy(slots, n):
     """slots: (CopySlot * k) host array; copies the first n (src -> dst, with fp32 <-> fp64 conversion) in one launch"""
-    _check(_lib.nmf_multi_copy(slots, n, _stream()), "nmf_multi_copy")
+    return HOST_EXT.multi_copy(C.addressof(slots), int(n), _stream())
 
 
 # ---- evaluation metrics (renderer.py:195-560) -----------------------------------------------------------------------
@@ -1314,237 +1064,3 @@ def material_maps(app, normals, weight, offsets, rays, head_W, head_b, head_p, c
                                   _p(incoming, torch.float32), _p(brdf_weight, torch.float32), C.c_int64(R),
                                   _p(acc, torch.float32), _p(bg, torch.float32), _p(out), _stream()), "nmf_material_maps")
     return out
-
-
-# ---- host-side fast path ---------------------------------------------------------------------------------------------
-# lib/_nmf_host.so (csrc/host_ext.cpp) implements the forward wrappers above in C++ -- same argument order, same outputs,
-# same checks, same C-ABI entry points -- at ~3 us per call instead of 10-25 us of Python (output allocation, checked
-# pointers, ctypes marshalling).  When the module is present its functions replace the Python definitions; the latter
-# stay reachable as PY_WRAPPERS[name] (tests compare both) and NMF_HOST_EXT=0 disables the replacement.
-PY_WRAPPERS = {}
-HOST_EXT = None
-
-
-def _load_host_ext():
-    if os.environ.get("NMF_HOST_EXT", "1") == "0":
-        return None
-    path = os.path.join(_HERE, "lib", "_nmf_host.so")
-    if not os.path.exists(path):
-        return None
-    try:
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("_nmf_host", path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        if mod.abi_version() != version():
-            return None
-        mod.set_error_class(NmfHipError)
-        return mod
-    except Exception:                   # stale build, missing torch symbols, ...: the Python wrappers do the same job
-        return None
-
-
-def _install_host_ext():
-    global HOST_EXT
-    fx = HOST_EXT = _load_host_ext()
-    if fx is None:
-        return
-    g = globals()
-    addr = C.addressof
-
-    def march_count(p, rays, jitter, alpha_bits, alpha_coarse=None):
-        return fx.march_count(addr(p), rays, jitter, alpha_bits, alpha_coarse, _stream())
-
-    def march_scan(counts, max_samples):
-        return fx.march_scan(counts, int(max_samples), _stream())
-
-    def march_fill(p, rays, b, M, jitter, valid, offsets, want_z=True):
-        return fx.march_fill(addr(p), rays, b, M, jitter, valid, offsets, want_z, _stream())
-
-    py_vm_query_fwd = g["vm_query_fwd"]
-
-    def vm_query_fwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, want_density=True, want_normal=True,
-                     want_app=True, want_coef=False):
-        if app_planes[0].dtype != torch.float32:       # bf16 tables: the ctypes wrapper dispatches on the table dtype
-            return py_vm_query_fwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, want_density, want_normal, want_app,
-                                   want_coef)
-        return fx.vm_query_fwd(addr(p), xyzt, dpk, dlk, app_planes, app_lines, basis, want_density, want_normal,
-                               want_app, want_coef, _stream())
-
-    def composite_fwd(sigma, dist, offsets, b, distance_scale):
-        return fx.composite_fwd(sigma, dist, offsets, b, distance_scale, _stream())
-
-    def segment_sum(vals, scale, offsets, n_seg, lanes=1):
-        return fx.segment_sum(vals, scale, offsets, n_seg, lanes, _stream())
-
-    def sat_lookup_fwd(sat, dirs, sa, mipbias, pole_rows, sc=None):
-        return fx.sat_lookup_fwd(sat, dirs, sa, mipbias, pole_rows, sc, _stream())
-
-    def select_bounces(weights, u, mode, mul, add=0.0, sum_w=1.0):
-        dev_sum = sum_w if isinstance(sum_w, torch.Tensor) else None
-        return fx.select_bounces(weights, u, mode, mul, add, 1.0 if dev_sum is not None else sum_w, dev_sum, _stream())
-
-    def expand_segments(offsets, n_seg, total):
-        return fx.expand_segments(offsets, n_seg, total, _stream())
-
-    def brdf_mlp_fwd(weights, half_vec, diff_vec, feat_src, rough_src, src_idx, out_bias, max_workgroups=0, with_mask=False, image=None):
-        r = fx.brdf_mlp_fwd(list(weights or ()), half_vec, diff_vec, feat_src, rough_src, src_idx, out_bias, bool(with_mask),
-                            int(max_workgroups), _stream(), image)
-        return r if with_mask else r[0]
-
-    def brdf_mlp_pack(weights, into=None):
-        return fx.brdf_mlp_pack(list(weights), into, _stream())
-
-    def heads_fwd(feat, W, b, hp):
-        return fx.heads_fwd(feat, W, b, list(hp), _stream())
-
-    def ggx_rays_fwd(V, N, r, x, off, cnt, sobol, row_of_ray, j_of_ray):
-        return fx.ggx_rays_fwd(V, N, r, x, off, cnt, sobol, row_of_ray, j_of_ray, _stream())
-
-    def shade_mix_fwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf):
-        return fx.shade_mix_fwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, _stream())
-
-    def bounce_index(counts, xyzt=None):
-        return fx.bounce_index(counts, xyzt, _stream())
-
-    def bounce_prep_fwd(bidx, normals, app, heads, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough, row_inputs=False):
-        return fx.bounce_prep_fwd(bidx, normals, app, heads, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough,
-                                  int(row_inputs), _stream())
-
-    def ray_compose_fwd(weight, refl_rows, inv, normals, rays, offsets, B, bg, bg_per_ray, tonemap, noclip, want_ori):
-        return fx.ray_compose_fwd(weight, refl_rows, inv, normals, rays, offsets, B, bg, bool(bg_per_ray), bool(tonemap),
-                                  bool(noclip), bool(want_ori), _stream())
-
-    def composite_bwd(sigma, dist, weight, offsets, b, distance_scale, d_weight):
-        return fx.composite_bwd(sigma, dist, weight, offsets, b, distance_scale, d_weight, _stream())
-
-    def segment_sum_wide(vals, D, offsets, n_seg):
-        return fx.segment_sum_wide(vals, D, offsets, n_seg, _stream())
-
-    py_sat_lookup_bwd = g["sat_lookup_bwd"]
-
-    def sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, want_dirs=True, want_mipbias=None, sc=None):
-        if want_mipbias is not None:      # legacy return form (tests): the Python wrapper
-            return py_sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, want_mipbias, sc)
-        return fx.sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, sc,
-                                 int(g["ENV_BINNED_MIN_LOOKUPS"]), _stream())
-
-    def brdf_mlp_bwd(weights, half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_out, act_mask, d_out, grads,
-                     max_workgroups=0, image=None):
-        return fx.brdf_mlp_bwd(list(weights or ()), half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_out, act_mask, d_out,
-                               list(grads), int(max_workgroups), _stream(), image)
-
-    def heads_bwd(feat, W, b, hp, d_out, gW, gb, add_into=None):
-        return fx.heads_bwd(feat, W, b, list(hp), d_out, gW, gb, add_into, _stream())
-
-    def ggx_rays_bwd(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays=None):
-        return fx.ggx_rays_bwd(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays, _stream())
-
-    def shade_mix_bwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows):
-        return fx.shade_mix_bwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows, _stream())
-
-    def ray_compose_bwd(weight, refl_rows, inv, normals, rays, ray_id, bg, bg_per_ray, tonemap, noclip, rgb_lin, d_rgb_map,
-                        d_acc, d_ori, want_d_normals):
-        return fx.ray_compose_bwd(weight, refl_rows, inv, normals, rays, ray_id, bg, bool(bg_per_ray), bool(tonemap),
-                                  bool(noclip), rgb_lin, d_rgb_map, d_acc, d_ori, bool(want_d_normals), _stream())
-
-    def vm_query_bwd_segments(p, segs, dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines,
-                              g_basis=None, plan=None, clean=None):
-        if clean is not None:
-            return fx.vm_query_bwd_clean(addr(p), list(segs), dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes,
-                                         g_app_lines, g_basis, clean, _stream())
-        if plan is not None:
-            return fx.vm_query_bwd_planned(addr(p), list(segs), dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes,
-                                           g_app_lines, g_basis, plan, _stream())
-        return fx.vm_query_bwd_segments(addr(p), list(segs), dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes,
-                                        g_app_lines, g_basis, _stream())
-
-    def vm_query_rows(p, xyzt, dpk, dlk):
-        return fx.vm_query_rows(addr(p), xyzt, list(dpk), list(dlk), _stream())
-
-    def vm_query_sigma(p, xyzt, planes, lines):
-        return fx.vm_query_sigma(addr(p), xyzt, list(planes), list(lines), _stream())
-
-    def sqerr_fwd(pred, gt):
-        return fx.sqerr_fwd(pred, gt, _stream())
-
-    def sqerr_bwd(pred, gt, d_out):
-        return fx.sqerr_bwd(pred, gt, d_out, _stream())
-
-    def shade_mix_bwd_view(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows):
-        return fx.shade_mix_bwd_view(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_rows, _stream())
-
-    def ggx_rays_bwd_view(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays=None):
-        return fx.ggx_rays_bwd_view(V, N, r, off, sobol, row_of_ray, j_of_ray, dL, d_rays, _stream())
-
-    def view_adjoint_to_rays(ray_id, bidx, dv_a, dv_b, d_rays):
-        return fx.view_adjoint_to_rays(ray_id, bidx, dv_a, dv_b, d_rays, _stream())
-
-    def select_total(weights, u, extra):
-        dev = weights.device
-        return fx.select_total(weights, u, float(extra), g["select_total_workspace"](dev), _stream())
-
-    def bounce_prep_bwd(inv, normals, heads, ray_id, rays, conv, min_rough, detach_n, dN, dr1, df0, ddiff, dfeat,
-                        bidx=None, row_inputs=False):
-        return fx.bounce_prep_bwd(inv, normals, heads, ray_id, rays, conv, float(min_rough), bool(detach_n), dN, dr1, df0, ddiff,
-                                  dfeat, bidx, int(row_inputs), _stream())
-
-    def adam_step(slots, n, guard=None):
-        return fx.adam_step(C.addressof(slots), int(n), guard, _stream())
-
-    def multi_copy(slots, n):
-        return fx.multi_copy(C.addressof(slots), int(n), _stream())
-
-    def loss_mix_bwd(shapes, weights, scale, d_out):
-        return fx.loss_mix_bwd([list(s_) for s_ in shapes], [float(v) for v in weights], float(scale), d_out, _stream())
-
-    py_l1_bwd, py_sat_bwd, py_sat_build, py_sh, py_pack = (g["l1_mean_bwd"], g["sat_build_bwd"], g["sat_build"], g["sh_project"],
-                                                          g["vm_pack_density"])
-
-    def l1_mean_bwd(tensors, d_out, out=None):
-        if out is None:
-            return py_l1_bwd(tensors, d_out, out)
-        fx.l1_mean_bwd_into(list(tensors), d_out, list(out), _stream())
-        return out
-
-    def sat_build_bwd(d_sat, bg_mat, act, d_pole, brightness=0.0, mul=1.0, sc=None, out=None):
-        if out is None or not bg_mat.is_contiguous():
-            return py_sat_bwd(d_sat, bg_mat, act, d_pole, brightness, mul, sc, out)
-        fx.sat_build_bwd_into(d_sat, bg_mat, act, d_pole, float(brightness), float(mul), sc, out, _stream())
-        return out
-
-    def sat_build(bg_mat, brightness=0.0, mul=1.0, sc=None, out=None, pole=False, interleaved=False):
-        if out is None or not bg_mat.is_contiguous():
-            return py_sat_build(bg_mat, brightness, mul, sc, out, pole, interleaved)
-        fx.sat_build_into(bg_mat, float(brightness), float(mul), sc, out[0], out[1], out[2] if pole else None,
-                          out[-1] if interleaved else None, _stream())
-        return (out[0], out[1]) + ((out[2],) if pole else ()) + ((out[-1],) if interleaved else ())
-
-    def sh_project(vals, wq, sh_A, out=None):
-        if out is None:
-            return py_sh(vals, wq, sh_A, out)
-        fx.sh_project_into(vals, wq, sh_A, out[0], out[1], _stream())
-        return out
-
-    def vm_pack_density(p, planes, lines, out=None):
-        if out is None:
-            return py_pack(p, planes, lines, out)
-        fx.vm_pack_density_into(addr(p), list(planes), list(lines), list(out[0]), list(out[1]), _stream())
-        return out
-
-    py_unpack = g["vm_unpack_density_grad"]
-
-    def vm_unpack_density_grad(p, g_dpk, g_dlk, out=None, l1=None):
-        if out is not None or l1 is not None:
-            return py_unpack(p, g_dpk, g_dlk, out, l1)
-        return fx.vm_unpack_density_grad(addr(p), g_dpk, g_dlk, _stream())
-
-    for name, fn in list(locals().items()):
-        if callable(fn) and name in g and name not in ("fx", "addr", "g", "py_sat_lookup_bwd", "py_unpack", "py_l1_bwd", "py_sat_bwd", "py_sat_build", "py_sh",
-                                                             "py_pack"):
-            PY_WRAPPERS[name] = g[name]
-            fn.__doc__ = g[name].__doc__
-            g[name] = fn
-
-
-_install_host_ext()

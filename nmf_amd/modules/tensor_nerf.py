@@ -141,7 +141,7 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
                 TensorNeRF._warned_fallback = True
                 import warnings
                 warnings.warn("TensorNeRF.forward(is_train=True) left the fused training pass for the operator graph (a call outside "
-                              "the pass: non-default arguments, no host extension, a chunk without bounce rows, or a second pending "
+                              "the pass: non-default arguments, a chunk without bounce rows, or a second pending "
                               "forward); `nerf.operator_graph_forwards` counts these calls", RuntimeWarning, stacklevel=3)
         if recur == 0:          # one gradient pass: primary and re-traced rays share the table-gradient nodes
             passes = [m for m in (self.rf, self.bg_module, getattr(self.model, "brdf", None),
@@ -178,7 +178,7 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
 
     def _forward_fused(self, rays, focal, bg_col, noise):
         """the training forward as ONE autograd node (fast_step.ChunkPass): -> (images, stats) like _render, or None when the pass
-        does not cover this call (configuration, no host extension, a chunk without a bounce row): the caller then builds the
+        does not cover this call (configuration, a chunk without a bounce row): the caller then builds the
         operator graph.  What a training loop reads of the result (train.py:541-577): rgb_map, whole_valid, n_samples, ori_loss,
         prediction_loss -- and the three zero-weight regularisers, see regulariser_stats."""
         from ..fast_step import TrainPass, Unsupported

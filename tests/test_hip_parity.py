@@ -1018,17 +1018,16 @@ def test_vm_value_only_query_and_row_normals():
     assert float(g1[0][outside].abs().max()) == 0.0 and float(g2[0].abs().max()) > 0          # nothing outside the rows
     assert torch.equal(g1[1], g2[1]) and torch.equal(g1[2], g2[2])
     # the row preparation's adjoint inside the heads' backward (nmf_bounce_prep_heads_bwd) = nmf_bounce_prep_bwd + nmf_heads_bwd
-    if hip.HOST_EXT is not None:
-        gW_a, gb_a = torch.zeros(11, 24, device=DEV), torch.zeros(11, device=DEV)
-        gW_b, gb_b = torch.zeros(11, 24, device=DEV), torch.zeros(11, device=DEV)
-        d_app_a = hip.heads_bwd(app, hW, hb, hp, g2[1], gW_a, gb_a, add_into=g2[2].clone())
-        stream = torch.cuda.current_stream().cuda_stream
-        dn_b, d_app_b = hip.HOST_EXT.bounce_prep_heads_bwd(bidx, nr_rows, heads, ray_id, rays, conv, 0.02, False, dN, dr1, df0, dd, dfeat,
-                                                           app, hW, hb, list(hp), gW_b, gb_b, stream)
-        assert torch.equal(dn_b, g2[0])
-        assert_close(d_app_b.cpu(), d_app_a.cpu(), rtol=1e-6, atol=1e-7 * float(d_app_a.abs().max()), what="fused row adjoint: d_app")
-        assert_close(gW_b.cpu(), gW_a.cpu(), rtol=1e-5, atol=1e-6 * float(gW_a.abs().max()), what="fused row adjoint: head weights")
-        assert_close(gb_b.cpu(), gb_a.cpu(), rtol=1e-5, atol=1e-6 * float(gb_a.abs().max()), what="fused row adjoint: head biases")
+    gW_a, gb_a = torch.zeros(11, 24, device=DEV), torch.zeros(11, device=DEV)
+    gW_b, gb_b = torch.zeros(11, 24, device=DEV), torch.zeros(11, device=DEV)
+    d_app_a = hip.heads_bwd(app, hW, hb, hp, g2[1], gW_a, gb_a, add_into=g2[2].clone())
+    stream = torch.cuda.current_stream().cuda_stream
+    dn_b, d_app_b = hip.HOST_EXT.bounce_prep_heads_bwd(bidx, nr_rows, heads, ray_id, rays, conv, 0.02, False, dN, dr1, df0, dd, dfeat,
+                                                       app, hW, hb, list(hp), gW_b, gb_b, stream)
+    assert torch.equal(dn_b, g2[0])
+    assert_close(d_app_b.cpu(), d_app_a.cpu(), rtol=1e-6, atol=1e-7 * float(d_app_a.abs().max()), what="fused row adjoint: d_app")
+    assert_close(gW_b.cpu(), gW_a.cpu(), rtol=1e-5, atol=1e-6 * float(gW_a.abs().max()), what="fused row adjoint: head weights")
+    assert_close(gb_b.cpu(), gb_a.cpu(), rtol=1e-5, atol=1e-6 * float(gb_a.abs().max()), what="fused row adjoint: head biases")
 
 
 @pytest.mark.parametrize("M", [1, 31, 33, 5000])
@@ -1677,7 +1676,7 @@ def test_vm_backward_segments_equal_concatenation(with_app):
 def test_vm_backward_with_a_plan_of_the_forward_equals_the_self_sorting_walk(with_app, grid):
     """nmf_vm_bin_plan (the brick sort, from the positions alone) + nmf_vm_query_bwd_planned accumulate what
     nmf_vm_query_bwd_segments does when it sorts by itself (autograd of fields/tensoRF.py:181-205); the plan is reusable
-    (two walks with different adjoints over one plan), through the Python wrappers and the host extension."""
+    (two walks with different adjoints over one plan)."""
     from nmf_amd import hip, synthetic
     G = grid
     cfg = O.Cfg(grid=G)
@@ -1714,28 +1713,27 @@ def test_vm_backward_with_a_plan_of_the_forward_equals_the_self_sorting_walk(wit
 
     flat = lambda t: torch.cat([x.reshape(-1) for x in (t[0] + t[1] + t[2] + t[3] + [t[4]])]).cpu()  # noqa: E731
     plan = hip.vm_bin_plan(p, xyzs)
-    for impl in ([hip.vm_query_bwd_segments] + ([hip.PY_WRAPPERS["vm_query_bwd_segments"]] if hip.HOST_EXT is not None else [])):
-        for seed in (1, 2):
-            segs = make_segs(seed)
-            a, b = bufs(), bufs()
-            impl(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None)
-            impl(p, segs, dpk, dlk, apl, ali, basis, b[0], b[1], b[2], b[3], b[4] if with_app else None, plan=plan)
-            fa, fb = flat(a), flat(b)
-            assert fa.abs().max() > 0
-            assert_close(fb, fa, rtol=2e-5, atol=2e-5 * float(fa.abs().max()), what="planned walk vs self-sorting walk")
+    impl = hip.vm_query_bwd_segments
+    for seed in (1, 2):
+        segs = make_segs(seed)
+        a, b = bufs(), bufs()
+        impl(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None)
+        impl(p, segs, dpk, dlk, apl, ali, basis, b[0], b[1], b[2], b[3], b[4] if with_app else None, plan=plan)
+        fa, fb = flat(a), flat(b)
+        assert fa.abs().max() > 0
+        assert_close(fb, fa, rtol=2e-5, atol=2e-5 * float(fa.abs().max()), what="planned walk vs self-sorting walk")
     # the counters of the sort in a scratch the caller keeps (nmf_vm_query_bwd_segments_clean): zero before, zero after, the same
     # gradients walk after walk (each walk hands the scratch back zero instead of being preceded by memset launches)
-    for impl in ([hip.vm_query_bwd_segments] + ([hip.PY_WRAPPERS["vm_query_bwd_segments"]] if hip.HOST_EXT is not None else [])):
-        clean = hip.vm_bwd_clean_scratch(p, DEV)
-        assert clean.numel() == hip._lib.nmf_vm_bwd_clean_bytes(G) and int(clean.count_nonzero()) == 0
-        for seed in (1, 2, 3):
-            segs = make_segs(seed)
-            a, b = bufs(), bufs()
-            impl(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None)
-            impl(p, segs, dpk, dlk, apl, ali, basis, b[0], b[1], b[2], b[3], b[4] if with_app else None, clean=clean)
-            fa, fb = flat(a), flat(b)
-            assert_close(fb, fa, rtol=2e-5, atol=2e-5 * float(fa.abs().max()), what="walk on a kept scratch vs walk with memsets")
-            assert int(clean.count_nonzero()) == 0, "the scratch must come back zero"
+    clean = hip.vm_bwd_clean_scratch(p, DEV)
+    assert clean.numel() == hip._lib.nmf_vm_bwd_clean_bytes(G) and int(clean.count_nonzero()) == 0
+    for seed in (1, 2, 3):
+        segs = make_segs(seed)
+        a, b = bufs(), bufs()
+        impl(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None)
+        impl(p, segs, dpk, dlk, apl, ali, basis, b[0], b[1], b[2], b[3], b[4] if with_app else None, clean=clean)
+        fa, fb = flat(a), flat(b)
+        assert_close(fb, fa, rtol=2e-5, atol=2e-5 * float(fa.abs().max()), what="walk on a kept scratch vs walk with memsets")
+        assert int(clean.count_nonzero()) == 0, "the scratch must come back zero"
     with pytest.raises(hip.NmfHipError):                       # a scratch that is too small is refused
         hip.vm_query_bwd_segments(p, make_segs(1), dpk, dlk, apl, ali, basis, *bufs()[:4], bufs()[4] if with_app else None,
                                   clean=torch.zeros(64, dtype=torch.uint8, device=DEV))
@@ -1747,47 +1745,76 @@ def test_vm_backward_with_a_plan_of_the_forward_equals_the_self_sorting_walk(wit
 
 
 @pytest.mark.gpu
-def test_host_extension_matches_python_wrappers():
-    """lib/_nmf_host.so (csrc/host_ext.cpp) replaces the forward wrappers of hip.py with C++ ones over the same C ABI:
-    same outputs bit for bit, same error type."""
+def test_host_extension_wrappers_vs_cpu_references():
+    """The wrappers of hip.py that lib/_nmf_host.so (csrc/host_ext.cpp) implements, on one set of seeded inputs: optional outputs,
+    the package's error type on misuse, and each result against the CPU oracle (bit-equal for counts / indices, the tolerances of
+    test_vm_field_vs_oracle_random and test_composite_empty_and_long_segments for floats)."""
     from nmf_amd import hip, synthetic
-    if hip.HOST_EXT is None:
-        pytest.skip("host extension not built / disabled (NMF_HOST_EXT=0): the Python wrappers are the ones under test")
-    py = hip.PY_WRAPPERS
     g = torch.Generator().manual_seed(9)
     G = 32
     cfg = O.Cfg(grid=G)
     sd = synthetic.state_dict_s1(grid=G, bg_resolution=16, seed=1)
     tabs = _field_tables(hip, sd, cfg)
-    xyz = torch.cat([(torch.rand(3001, 3, generator=g) * 2 - 1) * 1.4, torch.zeros(3001, 1)], 1).to(DEV).contiguous()
-    a = hip.vm_query_fwd(*tabs[:1], xyz, *tabs[1:], want_coef=True)
-    b = py["vm_query_fwd"](*tabs[:1], xyz, *tabs[1:], want_coef=True)
-    for x, y in zip(a, b):
-        assert torch.equal(x, y)
+    xyz_c = torch.cat([(torch.rand(3001, 3, generator=g) * 2 - 1) * 1.4, torch.zeros(3001, 1)], 1)
+    xyz = xyz_c.to(DEV).contiguous()
+    sf, sg, gr, nr, ap, cf = hip.vm_query_fwd(*tabs[:1], xyz, *tabs[1:], want_coef=True)
+    g_o = O.density_gradient(sd, cfg, xyz_c)
+    cf_o = torch.cat(O.vm_products(*O._app_factors(sd), O.normalize_coord(cfg, xyz_c)), dim=0).T
+    assert_close(sf.cpu(), O.density_feature(sd, cfg, xyz_c), rtol=1e-5, atol=2e-5, what="sigma_feat")
+    assert_close(sg.cpu(), O.density(sd, cfg, xyz_c), rtol=2e-5, atol=1e-6, what="sigma")
+    assert_close(ap.cpu(), O.app_feature(sd, cfg, xyz_c), rtol=1e-5, atol=1e-5, what="app")
+    assert_close(cf.cpu(), cf_o, rtol=1e-5, atol=1e-5, what="app coefficients")
+    assert_close(gr.cpu(), g_o, rtol=1e-4, atol=2e-5 * float(g_o.abs().max()), what="density gradient")
+    # the unit normal where normalize() does not amplify round-off.  This field is flat away from the cube's faces (median |g| =
+    # 1e-6 of the largest), so "not tiny" is relative to the largest gradient: the tolerance of the raw gradient above, 2e-5
+    # max|g| per component, moves a unit normal by at most sqrt(3) * 2e-5 max|g| / |g| = 1.7e-4 < atol where |g| > 0.2 max|g|
+    gn = g_o.norm(dim=-1)
+    ok = gn > 0.2 * float(gn.max())
+    assert int(ok.sum()) > 500
+    assert_close(nr.cpu()[ok], O.normals(sd, cfg, xyz_c)[ok], rtol=1e-4, atol=2e-4, what="normals")
     a = hip.vm_query_fwd(*tabs[:1], xyz, *tabs[1:], want_density=False, want_normal=False)
     assert a[0] is None and a[2] is None and a[4].shape == (3001, 24)
-    # segmented sums, composite, bounce bookkeeping
+    # bounce bookkeeping against torch's nonzero / cumsum (models/microfacet.py:333-350), bit for bit
     counts = (torch.rand(5000, generator=g) < 0.2).int() * torch.randint(1, 9, (5000,), generator=g).int()
-    a, b = hip.bounce_index(counts.to(DEV)), py["bounce_index"](counts.to(DEV))
-    Mb = int(a[4][1])
-    assert torch.equal(a[4], b[4]) and torch.equal(a[0][:Mb], b[0][:Mb]) and torch.equal(a[1][:Mb + 1], b[1][:Mb + 1])
-    assert torch.equal(a[3], b[3]) and a[3].shape == (5000,)
+    a = hip.bounce_index(counts.to(DEV))
+    R, Mb = (int(v) for v in a[4].cpu())
+    rows = torch.nonzero(counts > 0).reshape(-1)
+    off_c = torch.zeros(rows.shape[0] + 1, dtype=torch.int64)
+    off_c[1:] = torch.cumsum(counts[rows].long(), 0)
+    inv_c = torch.full((5000,), -1, dtype=torch.int32)
+    inv_c[rows] = torch.arange(rows.shape[0], dtype=torch.int32)
+    assert len(a) == 5 and Mb == rows.shape[0] and R == int(counts.sum())
+    assert torch.equal(a[0][:Mb].cpu().long(), rows) and torch.equal(a[1][:Mb + 1].cpu(), off_c)
+    assert torch.equal(a[2][:Mb].cpu(), counts[rows]) and torch.equal(a[3].cpu(), inv_c) and a[3].shape == (5000,)
     off = a[1][:Mb + 1].contiguous()
-    R = int(a[4][0])
-    sa_, sb_ = hip.expand_segments(off, Mb, R), py["expand_segments"](off, Mb, R)
-    assert torch.equal(sa_[0], sb_[0]) and torch.equal(sa_[1], sb_[1])
-    vals = torch.randn(R, 3, generator=g).to(DEV)
+    seg, loc = hip.expand_segments(off, Mb, R)
+    seg_c = torch.repeat_interleave(torch.arange(Mb), counts[rows].long())
+    assert torch.equal(seg.cpu().long(), seg_c)
+    assert torch.equal(loc.cpu().long(), torch.cat([torch.arange(int(n)) for n in counts[rows]]))
+    # segmented sums (index order and the eight-lane tree) against a float64 sum
+    vals_c = torch.randn(R, 3, generator=g)
+    vals = vals_c.to(DEV)
+    ref = torch.zeros(Mb, 3, dtype=torch.float64).index_add_(0, seg_c, vals_c.double()).float()
     for lanes in (1, 8):
-        assert torch.equal(hip.segment_sum(vals, None, off, Mb, lanes=lanes), py["segment_sum"](vals, None, off, Mb, lanes=lanes))
-    sig, dist = torch.rand(R, generator=g).to(DEV), (torch.rand(R, generator=g) * 0.01).to(DEV)
-    wa, wb = hip.composite_fwd(sig, dist, off, Mb, 25.0), py["composite_fwd"](sig, dist, off, Mb, 25.0)
-    assert torch.equal(wa[0], wb[0]) and torch.equal(wa[1], wb[1])
-    u = torch.rand(R, generator=g).to(DEV)
-    assert torch.equal(hip.select_bounces(wa[0], u, 0, 64.0), py["select_bounces"](wa[0], u, 0, 64.0))
-    # misuse raises the package's error type from both paths
-    for fn in (hip.composite_fwd, py["composite_fwd"]):
-        with pytest.raises(hip.NmfHipError):
-            fn(sig.cpu(), dist, off, Mb, 25.0)
+        assert_close(hip.segment_sum(vals, None, off, Mb, lanes=lanes).cpu(), ref, rtol=1e-5, atol=1e-5, what=f"segment_sum, {lanes} lanes")
+    # compositing against the oracle on the dense [row, step] layout (a padded step has sigma 0: alpha 0, T unchanged)
+    sig_c, dist_c = torch.rand(R, generator=g), torch.rand(R, generator=g) * 0.01
+    sig, dist = sig_c.to(DEV), dist_c.to(DEV)
+    w, acc = hip.composite_fwd(sig, dist, off, Mb, 25.0)
+    mask = torch.arange(8)[None] < counts[rows][:, None]
+    sig_d, dist_d = torch.zeros(Mb, 8), torch.zeros(Mb, 8)
+    sig_d[mask], dist_d[mask] = sig_c, dist_c
+    wo = O.raw2alpha(sig_d, dist_d * 25)
+    assert_close(w.cpu(), wo[mask], rtol=5e-6, atol=2e-7, what="weights")
+    assert_close(acc.cpu(), wo.sum(1), rtol=1e-5, atol=1e-6, what="acc")
+    # level-0 bounce selection against the oracle's (pt_selectors.py:20-22), bit for bit on the GPU's weights
+    u_c = torch.rand(R, generator=g)
+    c = hip.select_bounces(w, u_c.to(DEV), 0, 64.0).cpu().long()
+    bounce, ray_mask = O.select_bounces(w.cpu(), torch.ones(R, dtype=torch.bool), None, 64.0, O.Noise(tape=[("rand", u_c)]))
+    assert torch.equal(c > 0, bounce) and torch.equal(c[c > 0], ray_mask.sum(1)) and int(bounce.sum()) > 0
+    # misuse raises the package's error type
+    with pytest.raises(hip.NmfHipError):
+        hip.composite_fwd(sig.cpu(), dist, off, Mb, 25.0)
     with pytest.raises(hip.NmfHipError):
         hip.segment_sum(vals, None, off, Mb, lanes=3)
 
