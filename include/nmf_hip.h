@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 118
+#define NMF_ABI_VERSION 119
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -723,6 +723,43 @@ int nmf_material_maps(const float* app, const float* normals, const float* weigh
                       float tint_bias, float f0_bias, float rough_bias, const float* conv, const int32_t* inv,
                       const int64_t* row_off, const int32_t* cnt, int64_t Mb, const float* incoming, const float* brdf_weight,
                       int64_t R, const float* acc, const float* bg, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mesh export: indexed marching cubes over a dense volume (the reference's scripts/export_mesh.py runs
+ * skimage.measure.marching_cubes on the host through utils.convert_sdf_samples_to_ply).  Not on the training path.
+ * vol [gx][gy][gz] fp32, C order (what AlphaGridSampler.getDenseAlpha returns), every axis 2..1024 points (else NMF_ERANGE), flat
+ * indices int64.  A lattice point is inside when vol > level; a NaN is outside.
+ *
+ * One vertex per lattice edge whose two ends differ in insideness, owned by the lattice point n = (i gy + j) gz + k at the edge's
+ * lower end (a point owns its +x, +y, +z edges, in this order).  Position along the edge's axis, in lattice index units, fp32 with
+ * one rounding per operation: p = i + (level - a) / (b - a), a = vol at the owner, b = vol at the other end (a NaN or infinite
+ * end gives a NaN coordinate).  Faces are int32 triples of vertex indices; their normals point from inside to outside (a closed
+ * blob has a positive signed volume sum(det[p0, p1, p2]) / 6, the reference's orientation after its faces[..., ::-1]).
+ *
+ * Cases: corner c = dx + 2 dy + 4 dz of the cell at n, bit c of the case byte = that corner is inside; corners past the volume
+ * repeat the last point of their axis (the points of the upper faces own edges but no triangles).  Edge e = 4 axis + k runs along
+ * axis (0 x, 1 y, 2 z) from the corner whose two other coordinates are (k & 1, k >> 1), in the order of the remaining axes.
+ * The 256-case table (csrc/mc_table.hpp) is generated by tools/gen_mc_table.py; on a face with four crossings every inside corner is
+ * cut off by its own segment, a rule of the face's four signs only, so neighbouring cells agree (no holes).
+ *
+ * nmf_mc_count: cases [N] uint8, vcount [N] int32 (owned vertices, 0..3), tcount [N] int32 (triangles, 0..5), N = gx gy gz, in
+ * lattice order.  The caller replaces vcount / tcount by their INCLUSIVE sums in that order (in place: the scan is plumbing, e.g.
+ * torch.cumsum), reads back the two totals V and F and allocates verts [V][3] fp32 and faces [F][3] int32.
+ * nmf_mc_emit: point n writes its vertices from vscan[n - 1] and its faces from tscan[n - 1] (0 for n == 0); a face finds a
+ * neighbour's vertex through that neighbour's case byte and scanned base.  No atomics: the output order is the lattice order, two
+ * runs give identical bytes.  NMF_ERANGE if n_verts or 3 n_faces passes 2^31 - 1.  Stores are checked against n_verts / n_faces.
+ * V == 0 and F == 0: no launch, verts / faces may be NULL.  One launch each.
+ * nmf_mc_workspace_bytes: 9 bytes per lattice point (cases + vcount + tcount), the working memory beyond the volume and the
+ * outputs; 0 for a non-positive size.  Host arithmetic.
+ * nmf_mc_case_triangles: host only.  Writes the edge triples of one case (-1 padded) and returns its triangle count (0..5), or a
+ * negative code.
+ * ---------------------------------------------------------------------------------------- */
+int nmf_mc_count(const float* vol, int32_t gx, int32_t gy, int32_t gz, float level, uint8_t* cases, int32_t* vcount,
+                 int32_t* tcount, void* stream);
+int nmf_mc_emit(const float* vol, int32_t gx, int32_t gy, int32_t gz, float level, const uint8_t* cases, const int32_t* vscan,
+                const int32_t* tscan, int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces, void* stream);
+int64_t nmf_mc_workspace_bytes(int32_t gx, int32_t gy, int32_t gz);
+int nmf_mc_case_triangles(int case_index, int8_t out[16]);
 
 #ifdef __cplusplus
 }

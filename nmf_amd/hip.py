@@ -96,6 +96,7 @@ EXPORTS = [
     "nmf_retrace_scores", "nmf_argsort_f32", "nmf_argsort_workspace_bytes", "nmf_topk_select", "nmf_topk_select_workspace_bytes", "nmf_alpha_coarse", "nmf_alpha_coarse_words", "nmf_bounce_index_select", "nmf_bounce_prep_fwd_heads", "nmf_bounce_prep_heads_bwd", "nmf_multi_copy",
     "nmf_ssim", "nmf_ssim_workspace_bytes", "nmf_normal_err", "nmf_normal_err_workspace_bytes",
     "nmf_material_maps",
+    "nmf_mc_count", "nmf_mc_emit", "nmf_mc_workspace_bytes", "nmf_mc_case_triangles",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -149,6 +150,7 @@ _lib.nmf_alpha_coarse_words.restype = C.c_int64
 _lib.nmf_sat_lookup_bwd_workspace_bytes.restype = C.c_int64
 _lib.nmf_ssim_workspace_bytes.restype = C.c_int64
 _lib.nmf_normal_err_workspace_bytes.restype = C.c_int64
+_lib.nmf_mc_workspace_bytes.restype = C.c_int64
 
 
 def version():
@@ -1064,3 +1066,59 @@ def material_maps(app, normals, weight, offsets, rays, head_W, head_b, head_p, c
                                   _p(incoming, torch.float32), _p(brdf_weight, torch.float32), C.c_int64(R),
                                   _p(acc, torch.float32), _p(bg, torch.float32), _p(out), _stream()), "nmf_material_maps")
     return out
+
+
+# ---- mesh export: marching cubes over a dense volume (csrc/mesh.hip) ------------------------------------------------------
+MC_INDEX_MAX = 2 ** 31 - 1          # faces are int32 indices: V and 3 F stay below
+
+
+def mc_case_triangles(case_index):
+    """the edge triples of one of the 256 cases (host table lookup) -> list of (e0, e1, e2); edge and corner numbering: nmf_hip.h"""
+    out = (C.c_int8 * 16)()
+    n = _lib.nmf_mc_case_triangles(C.c_int(int(case_index)), out)
+    if n < 0:
+        raise NmfHipError(f"nmf_mc_case_triangles failed: {_lib.nmf_last_error_string().decode()} [{n}]")
+    return [tuple(out[3 * t:3 * t + 3]) for t in range(n)]
+
+
+def mc_count(vol, level):
+    """count pass -> (cases uint8 [N], vcount int32 [N], tcount int32 [N]), views of ONE workspace of nmf_mc_workspace_bytes"""
+    ptr = _p(vol, torch.float32)
+    if vol.dim() != 3:
+        raise NmfHipError(f"marching cubes: the volume is [Gx, Gy, Gz], got {tuple(vol.shape)}")
+    g = [int(v) for v in vol.shape]
+    n = g[0] * g[1] * g[2]
+    ws = torch.empty(max(int(_lib.nmf_mc_workspace_bytes(*g)), 16), dtype=torch.uint8, device=vol.device)
+    vcount, tcount, cases = ws[:4 * n].view(torch.int32), ws[4 * n:8 * n].view(torch.int32), ws[8 * n:9 * n]
+    _check(_lib.nmf_mc_count(ptr, *g, C.c_float(float(level)), _p(cases), _p(vcount), _p(tcount), _stream()), "nmf_mc_count")
+    return cases, vcount, tcount
+
+
+def mc_emit(vol, level, cases, vscan, tscan, n_verts, n_faces):
+    """emit pass over the INCLUSIVE sums of mc_count's counts -> (verts fp32 [V, 3], faces int32 [F, 3])"""
+    g = [int(v) for v in vol.shape]
+    verts = torch.empty((n_verts, 3), dtype=torch.float32, device=vol.device)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=vol.device)
+    _check(_lib.nmf_mc_emit(_p(vol, torch.float32), *g, C.c_float(float(level)), _p(cases, torch.uint8), _p(vscan, torch.int32),
+                            _p(tscan, torch.int32), C.c_int64(n_verts), C.c_int64(n_faces), _p(verts), _p(faces), _stream()),
+           "nmf_mc_emit")
+    return verts, faces
+
+
+def marching_cubes(vol, level):
+    """Indexed marching cubes of a dense fp32 device volume [Gx, Gy, Gz] at iso-level `level` (inside: vol > level) ->
+    (verts fp32 [V, 3] in lattice index units, faces int32 [F, 3], normals from inside to outside).  Vertices are welded (one per
+    sign-changing lattice edge) and the order is the lattice order: two runs give identical bytes.  Count pass, in-place scan of
+    the two counts (torch.cumsum: plumbing), ONE read-back of (V, F), emit pass.  An empty surface gives [0, 3] tensors."""
+    if not vol.is_cuda:
+        raise NmfHipError("nmf_amd operators need device tensors (no CPU path)")
+    vol = vol.contiguous()
+    cases, vcount, tcount = mc_count(vol, level)
+    # the totals in int64 (the int32 running sums would wrap silently on a volume that must be refused)
+    rb = Readback.of(vol.device).start(torch.stack([vcount.sum(), tcount.sum()]))
+    torch.cumsum(vcount, 0, dtype=torch.int32, out=vcount)
+    torch.cumsum(tcount, 0, dtype=torch.int32, out=tcount)
+    V, F = rb.get()
+    if V > MC_INDEX_MAX or 3 * F > MC_INDEX_MAX:
+        raise NmfHipError(f"marching cubes: {V} vertices / {F} faces do not fit int32 face indices (V and 3 F at most 2^31 - 1)")
+    return mc_emit(vol, level, cases, vcount, tcount, V, F)

@@ -24,7 +24,8 @@ TensorNeRF.load.
 Prints one JSON line per evaluation: iteration, train PSNR proxy (train.py:609-613), test PSNR with the reference's
 8-bit formula (renderer.py:399-401), rays/s.  --render-test (Blender scenes, train.py:861-875): after training, rank 0 evaluates
 every test view (renderer.evaluation: PSNR, SSIM, normal error, frames) into <logfolder>/imgs_test_all/ and prints one more line
-{"test_all": {"psnr", "ssim", "norm_err", "views"}}.
+{"test_all": {"psnr", "ssim", "norm_err", "views"}}.  --export-mesh: after training, rank 0 writes the alpha iso-surface with
+per-vertex normals and materials to <logfolder>/<expname>.ply (nmf_amd.export_mesh) and prints {"mesh": {"V", "F", "seconds", ...}}.
 """
 import argparse
 import json
@@ -113,6 +114,8 @@ def main(argv=None):
     ap.add_argument("--material-maps", action="store_true",
                     help="with --render-test: also write the material maps of every test view (albedo/, roughness/, tint/, diffuse/, "
                          "spec/, rgbd/)")
+    ap.add_argument("--export-mesh", action="store_true",
+                    help="after training: marching cubes of the alpha lattice into <logfolder>/<expname>.ply (nmf_amd.export_mesh)")
     ap.add_argument("-m", "--multirun", action="store_true",
                     help="hydra multirun (README.md:10): comma-separated override values span a sweep, run job by job")
     ap.add_argument("overrides", nargs="*", help="hydra-style tokens: group=name, a.b.c=value")
@@ -281,6 +284,11 @@ def main(argv=None):
         res = evaluation(te_all, nerf, None, None, os.path.join(logfolder, "imgs_test_all"), N_vis=-1, device=dev, noise=noise,
                          **(dict(material_maps=True) if args.material_maps else {}))
         print(json.dumps(dict(test_all=test_all_record(res))), flush=True)
+    if args.export_mesh and rank == 0:
+        from .export_mesh import export
+        os.makedirs(logfolder, exist_ok=True)
+        nerf.eval()
+        print(json.dumps(dict(mesh=export(nerf, os.path.join(logfolder, f"{expname}.ply")))), flush=True)
     if world > 1:
         dist.destroy_process_group()
     return cfg
