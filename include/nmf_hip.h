@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 119
+#define NMF_ABI_VERSION 120
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -760,6 +760,33 @@ int nmf_mc_emit(const float* vol, int32_t gx, int32_t gy, int32_t gz, float leve
                 const int32_t* tscan, int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces, void* stream);
 int64_t nmf_mc_workspace_bytes(int32_t gx, int32_t gy, int32_t gz);
 int nmf_mc_case_triangles(int case_index, int8_t out[16]);
+
+/* ------------------------------------------------------------------------------------------
+ * Total-variation regularisers (utils.py:139-151 TVLoss on the VM planes / lines, modules/integral_equirect.py:399-407 tv_loss on
+ * the environment map; train.py:684-709 adds them to every chunk's loss).  `count` (1..16) tensors in ONE launch:
+ *   value_out[0] = scale * sum_i w[i] * TV_i(x_i)                       (WRITTEN; NULL: gradient only)
+ *   g[i]        += scale * w[i] * dTV_i/dx_i                            (ADDED;   g == NULL: value only)
+ * shape [count][3] = (C, H, W) of x_i[1][C][H][W]; x_stride / g_stride [count][3]: element strides along C, H, W of x_i / g_i --
+ * any dense storage order (the field's tables are channel-last, a gradient accumulator may differ from its parameter), else
+ * NMF_EINVAL.  kind[i]:
+ *   NMF_TV_PLANE  mean over c, h < H-1, w < W-1 of sqrt(dw^2 + dh^2 + 1e-5), dh = x[h+1][w] - x[h][w], dw = x[h][w+1] - x[h][w];
+ *                 H < 2 or W < 2: NMF_ERANGE (the reference's mean over an empty set is NaN)
+ *   NMF_TV_LINE   W == 1: mean |x[g+1] - x[g]|, sign(0) = 0 in the gradient; H < 2: NMF_ERANGE
+ *   NMF_TV_ENVMAP C == 3, the reference's arithmetic on bg_mat[0] = [3][H][W] AS WRITTEN: mean over c < 2, h < H-1, all w of
+ *                 |x[c+1][h][w] - x[c][h][w]| + |x[c][h+1][w] - x[c][h][w]| + 1e-8; H < 2: NMF_ERANGE
+ * Terms and gradient in fp32 without contraction, the value as the fp64 sum of the terms: per-workgroup sums added in workgroup
+ * order by the workgroup that finishes last (no zero fill, no float atomics: run-to-run and stream-to-stream identical).  The
+ * gradient is a gather (each element's own term and its lower neighbours' terms): no atomics.  scale_dev: device scalar.
+ * workspace (only read with value_out): nmf_tv_workspace_bytes(shape, kind, count) bytes (or a negative code for a refused table),
+ * 16-byte aligned, whose first 4 bytes are ZERO before the first use (the ticket, left at zero again); one workspace serves one
+ * stream at a time.  A refused call launches nothing and writes nothing. */
+#define NMF_TV_PLANE 0
+#define NMF_TV_LINE 1
+#define NMF_TV_ENVMAP 2
+int64_t nmf_tv_workspace_bytes(const int32_t* shape, const int32_t* kind, int32_t count);
+int nmf_tv_fwd_bwd(const float* const x[], float* const g[], const int32_t* shape, const int64_t* x_stride, const int64_t* g_stride,
+                   const int32_t* kind, const float w[], int32_t count, const float* scale_dev, float* value_out, void* workspace,
+                   int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

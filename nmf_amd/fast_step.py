@@ -568,6 +568,40 @@ class TrainPass:
         a.early_pairs = [(prm, g) for prm, g in pairs if prm.requires_grad]
         return a.early_pairs
 
+    # ---- total-variation terms: once per optimizer step -----------------------------------------------------------------------
+    @torch.no_grad()
+    def add_tv(self, tensors, kinds, weights):
+        """behind end_step: value + gradient of the step's TV terms (trainer.tv_table) in ONE launch, the gradient ADDED to the tensors
+        end_step has just handed over as .grad (the parameter-shaped views of the flat accumulator) -> the weighted value (0-d)."""
+        grads = []
+        for t in tensors:
+            if t.grad is None:                   # the env map of a step that never looked it up: the zeros of the step's fill
+                bgm, a = self.nerf.bg_module, self._acc_cache
+                if t is not bgm.bg_mat or a is None:
+                    raise hip.NmfHipError("TV term of a parameter the step produced no gradient for")
+                t.grad = a.d_bg.reshape(t.shape)
+            grads.append(t.grad)
+        value, _ = hip.tv_value_grad(tensors, kinds, weights, 1.0, grads=grads)
+        return value
+
+    @torch.no_grad()
+    def add_env_tv(self, dev, scale):
+        """data parallel, behind prepare_early(behind_chunks=True) and in front of the early collective: this rank's share `scale` of
+        the env map's TV gradient is ADDED to the table gradient d_bg the collective sums -> the weighted value (0-d).  The table
+        backward of the step has been joined (or run by prepare_early) and is marked done: end_step must not write d_bg again."""
+        a = self.acc
+        e = self._early_env
+        if e is not None and e[0] != "done":     # queued by the last chunk's backward on its side stream
+            e[0].join_early_env()
+            self.join_contexts()
+        bgm = self.nerf.bg_module
+        if bgm.brightness_lr != 0 or bgm.mul_lr != 0:    # (end_step derives their gradients from d_bg, which the TV term is no part of)
+            raise NotImplementedError("data-parallel TV_weight_bg with a trainable env-map brightness / mul")
+        value, _ = hip.tv_value_grad([bgm.bg_mat], ["env"], [scale], 1.0, grads=[a.d_bg.reshape(bgm.bg_mat.shape)])
+        a.used_env = True
+        self._early_env = ("done", a.d_bg)
+        return value
+
     def _register_prefetch(self):
         """a training loop that is not the Trainer (the reference's train.py) steps its optimizer itself: behind FusedAdam.step()
         the next step's derived tables are queued on their side stream, as Trainer.step does after its own optimizer call"""

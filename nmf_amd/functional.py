@@ -722,6 +722,25 @@ class L1Mean(torch.autograd.Function):
         return (None,) + tuple(hip.l1_mean_bwd(list(ctx.saved_tensors), d_out.contiguous()))
 
 
+class TVWeighted(torch.autograd.Function):
+    """sum_i w_i TV_i(x_i) over [1,C,H,W] tensors in one launch per direction -- the counterpart of L1Mean for the reference's
+    total-variation terms (utils.py:139-151 on planes / lines, modules/integral_equirect.py:399-407 on the environment map).
+    kinds: 'plane' / 'line' / 'env' per tensor.  Forward is the value mode of nmf_tv_fwd_bwd, backward its gradient mode with the
+    incoming adjoint as the device-side scale."""
+
+    @staticmethod
+    def forward(ctx, kinds, weights, *tensors):
+        ctx.cfg = (tuple(kinds), tuple(float(w) for w in weights))
+        ctx.save_for_backward(*tensors)
+        return hip.tv_value(list(tensors), ctx.cfg[0], ctx.cfg[1], 1.0)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        kinds, weights = ctx.cfg
+        _, grads = hip.tv_value_grad(list(ctx.saved_tensors), kinds, weights, d_out.detach().float().contiguous(), value=False)
+        return (None, None) + tuple(grads)
+
+
 class LossMix(torch.autograd.Function):
     """scale * sum_i w_i * sum(x_i): the loss assembly of train.py:640-677 (photometric term, orientation and prediction
     regularisers as per-ray vectors, density L1) in one launch per direction instead of ~20 scalar kernels."""

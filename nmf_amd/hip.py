@@ -97,6 +97,7 @@ EXPORTS = [
     "nmf_ssim", "nmf_ssim_workspace_bytes", "nmf_normal_err", "nmf_normal_err_workspace_bytes",
     "nmf_material_maps",
     "nmf_mc_count", "nmf_mc_emit", "nmf_mc_workspace_bytes", "nmf_mc_case_triangles",
+    "nmf_tv_fwd_bwd", "nmf_tv_workspace_bytes",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -151,6 +152,7 @@ _lib.nmf_sat_lookup_bwd_workspace_bytes.restype = C.c_int64
 _lib.nmf_ssim_workspace_bytes.restype = C.c_int64
 _lib.nmf_normal_err_workspace_bytes.restype = C.c_int64
 _lib.nmf_mc_workspace_bytes.restype = C.c_int64
+_lib.nmf_tv_workspace_bytes.restype = C.c_int64
 
 
 def version():
@@ -944,6 +946,81 @@ def sqerr_fwd(pred, gt):
 def sqerr_bwd(pred, gt, d_out):
     """-> d_pred = 2 (pred - clip(gt)) d_out inside [0, 1], 0 outside (d_out: 0-d device tensor)"""
     return HOST_EXT.sqerr_bwd(pred, gt, d_out, _stream())
+
+
+# ---- total-variation regularisers --------------------------------------------------------------------
+TV_KINDS = {"plane": 0, "line": 1, "env": 2}
+_tv_ws = {}
+_tv_scale = {}
+
+
+def tv_kind(t):
+    """the kind utils.TVLoss applies to a [1,C,H,W] tensor (utils.py:143: a last dimension of 1 is a line)"""
+    return "line" if t.shape[-1] == 1 else "plane"
+
+
+def _tv_launch(tensors, kinds, weights, scale, grads, want_value):
+    """ONE nmf_tv_fwd_bwd launch over all tensors ([1,C,H,W] or [C,H,W] fp32 device tensors in any dense storage order)"""
+    n = len(tensors)
+    if not (n == len(kinds) == len(weights)) or (grads is not None and len(grads) != n):
+        raise NmfHipError("tv: tensors / kinds / weights / grads differ in length")
+    dev = tensors[0].device
+    shape, xs, gs = (C.c_int32 * (3 * n))(), (C.c_int64 * (3 * n))(), (C.c_int64 * (3 * n))()
+    for i, t in enumerate(tensors):
+        g = grads[i] if grads is not None else None
+        for u in (t, g):
+            if u is None:
+                continue
+            if u.dtype != torch.float32 or not u.is_cuda or u.device != dev:
+                raise NmfHipError("tv: expected float32 tensors on one device")
+            if u.dim() not in (3, 4) or (u.dim() == 4 and u.shape[0] != 1) or (u is g and u.shape[-3:] != t.shape[-3:]):
+                raise NmfHipError("tv: tensors are [1,C,H,W] (or [C,H,W]) and a gradient has its tensor's shape")
+        shape[3 * i:3 * i + 3] = list(t.shape[-3:])
+        xs[3 * i:3 * i + 3] = list(t.stride()[-3:])
+        if g is not None:
+            gs[3 * i:3 * i + 3] = list(g.stride()[-3:])
+    kind = (C.c_int32 * n)(*[TV_KINDS[k] if isinstance(k, str) else int(k) for k in kinds])
+    w = (C.c_float * n)(*[float(v) for v in weights])
+    if not isinstance(scale, torch.Tensor):
+        key = (dev, float(scale))
+        if key not in _tv_scale:
+            if len(_tv_scale) > 64:
+                _tv_scale.clear()
+            _tv_scale[key] = torch.full((), float(scale), dtype=torch.float32, device=dev)
+        scale = _tv_scale[key]
+    if scale.numel() != 1:
+        raise NmfHipError("tv: the scale is a single device value")
+    value, ws, ws_bytes = None, None, 0
+    if want_value:
+        need = int(_lib.nmf_tv_workspace_bytes(shape, kind, C.c_int32(n)))
+        _check(min(need, 0), "nmf_tv_workspace_bytes")
+        wkey = (dev, _stream())
+        ws = _tv_ws.get(wkey)
+        if ws is None or ws.numel() < need:                     # zeroed: the ticket is zero between launches
+            ws = _tv_ws[wkey] = torch.zeros(max(2 * need, 4096), dtype=torch.uint8, device=dev)
+        ws_bytes = ws.numel()
+        value = torch.empty((), dtype=torch.float32, device=dev)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    gptrs = (C.c_void_p * n)(*[g.data_ptr() for g in grads]) if grads is not None else None
+    _check(_lib.nmf_tv_fwd_bwd(ptrs, gptrs, shape, xs, gs if grads is not None else None, kind, w, C.c_int32(n),
+                               _p(scale.reshape(()), torch.float32), _p(value), None if ws is None else C.c_void_p(ws.data_ptr()),
+                               C.c_int64(ws_bytes), _stream()), "nmf_tv_fwd_bwd")
+    return value
+
+
+def tv_value_grad(tensors, kinds, weights, scale, grads=None, value=True):
+    """-> (scale * sum_i w_i TV_i(x_i) as a 0-d tensor, grads): value and gradient in ONE launch.  kinds: 'plane' / 'line' / 'env'
+    per tensor; scale: python float or 0-d device tensor.  grads: tensors to ADD scale * w_i * dTV_i/dx_i into (any dense storage
+    order of the tensor's shape); None: new zero tensors in the tensors' own memory order.  value=False: the gradient only (-> None, grads)."""
+    tensors = [t.detach() for t in tensors]
+    if grads is None:
+        grads = [torch.zeros_like(t, memory_format=torch.preserve_format) for t in tensors]
+    return _tv_launch(tensors, kinds, weights, scale, list(grads), bool(value)), grads
+
+
+def tv_value(tensors, kinds, weights, scale):
+    """-> scale * sum_i w_i TV_i(x_i) (0-d tensor): the value mode of the same launch, nothing else is written"""
+    return _tv_launch([t.detach() for t in tensors], kinds, weights, scale, None, True)
 
 
 # ---- retrace selection ------------------------------------------------------------------------------

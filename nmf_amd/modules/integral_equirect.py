@@ -152,6 +152,20 @@ class IntegralEquirect(FastPrivateAttrs, torch.nn.Module):
         err = ((X @ coef - Y) ** 2).clip(min=0, max=1)
         return float(-10.0 * torch.log10(err.mean()))
 
+    def tv_loss(self):
+        """modules/integral_equirect.py:399-407 AS WRITTEN: bg_mat[0] is [3,H,W], so `tv_h` is the difference of adjacent CHANNELS
+        over rows 0..H-2 and `tv_w` the row difference of channels 0 and 1 (the comment there says h, w, 3).  The
+        float32 device parameter is one kernel launch per direction, a CPU parameter evaluates the torch expression."""
+        if self.bg_mat.is_cuda:
+            if self.bg_mat.dtype != torch.float32:
+                raise NotImplementedError("tv_loss on the device takes the float32 environment map")
+            from ..functional import TVWeighted
+            return TVWeighted.apply(("env",), (1.0,), self.bg_mat)
+        img = self.bg_mat[0]
+        tv_h = (img[1:, :-1] - img[:-1, :-1]).abs()
+        tv_w = (img[:-1, 1:] - img[:-1, :-1]).abs()
+        return (tv_h + tv_w + 1e-8).mean()
+
     def forward(self, viewdirs, saSample, max_level=None):
         """viewdirs [R,3]; the build's callers may also hand over [R,6] ray rows (origin | direction): they are looked up
         along columns 3..5 in place, and the gradient comes back with the rays' own shape (no slice / pad kernels)."""

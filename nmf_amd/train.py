@@ -79,6 +79,8 @@ def compose_run(args, overrides):
         ov.append(f"N_vis={args.test_views}")
     if args.res is not None:
         ov.append(f"dataset.res={args.res}")
+    # `params.<key>=` is short for `model.params.<key>=` (the loss weights and schedules of configs/model/<name>.yaml:params)
+    overrides = [("model." + o.lstrip("+")) if o.lstrip("+").startswith("params.") else o for o in overrides]
     cfg = yaml_config.compose(args.config_dir, ov + list(overrides))
     if args.datadir:
         path = os.path.abspath(args.datadir)
@@ -228,7 +230,8 @@ def main(argv=None):
         from .trainer import broadcast_replica, check_replicas
         broadcast_replica(nerf, src=0)
         check_replicas(nerf, what="after the start-up broadcast")
-    trainer = Trainer(nerf, params, world_size=world, rank=rank)
+    trainer = Trainer(nerf, params, world_size=world, rank=rank, lr_decay_iters=int(cfg.get("lr_decay_iters", -1)),
+                      lr_decay_target_ratio=float(cfg.get("lr_decay_target_ratio", 0.1)))
     noise = DeviceNoise(dev, seed=1000 + rank)
     g = torch.Generator(device=dev).manual_seed(seed)        # same permutation on every rank
     n_total = rays_tr.shape[0]
@@ -267,7 +270,9 @@ def main(argv=None):
             if rank == 0:
                 print(json.dumps(dict(iteration=it + 1, train_psnr=round(out["psnr"], 3), test_psnr=round(psnr, 3),
                                       rays_per_s=round(rays_seen / (time.time() - t0), 1), num_rays=trainer.num_rays,
-                                      retrace=nerf.model.max_retrace_rays, n_samples=out["n_samples"])), flush=True)
+                                      retrace=nerf.model.max_retrace_rays, n_samples=out["n_samples"],
+                                      **({"tv": out["tv"], "operator_graph_forwards": getattr(nerf, "operator_graph_forwards", None)}
+                                         if trainer.tv.on else {}))), flush=True)
     save = args.save
     if save is None and not shorthand and not args.no_config_file:
         save = os.path.join(logfolder, f"{expname}.th")                                     # train.py:856 (tensorf.save)

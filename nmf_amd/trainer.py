@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 
 from .fast_step import Unsupported
-from .functional import LossMix, SquaredError
+from .functional import LossMix, SquaredError, TVWeighted
 from .optim import FusedAdam
 
 _CONST = {}
@@ -549,19 +549,101 @@ def check_replicas(nerf, group=None, what=""):
     return hi
 
 
+class TVSchedule:
+    """The weights of the three total-variation terms as train.py:292-295,684-709 moves them: `TV_weight_density` and
+    `TV_weight_app` are multiplied by lr_factor = lr_decay_target_ratio ** (1 / (lr_decay_iters if lr_decay_iters > 0 else n_iters))
+    once per chunk that reaches the loss, BEFORE that chunk uses them; `TV_weight_bg` is constant; every such chunk adds w / lbatch_size
+    times the term.  The terms depend on the parameters alone, which do not change inside an optimizer step: `sums` collects the
+    chunks' w / lbatch_size on the host and the step applies each term once.
+    Data parallel: the k-th loss chunk of rank r takes the weight of chunk k * world_size + r of the step, so that the ranks' sum is
+    the reference's sum over all chunks (equal chunk counts on the ranks)."""
+
+    def __init__(self, params, lr_decay_iters=-1, lr_decay_target_ratio=0.1, world_size=1, rank=0):
+        self.density = float(params.get("TV_weight_density") or 0.0)
+        self.app = float(params.get("TV_weight_app") or 0.0)
+        self.bg = float(params.get("TV_weight_bg") or 0.0)
+        iters = lr_decay_iters if lr_decay_iters is not None and lr_decay_iters > 0 else params["n_iters"]
+        self.lr_factor = float(lr_decay_target_ratio) ** (1 / iters)
+        self.world_size, self.rank = int(world_size), int(rank)
+        self.on = self.density > 0 or self.app > 0 or self.bg > 0
+        self.sums = [0.0, 0.0, 0.0]              # the step's shares, all chunks
+        self.in_graph = [0.0, 0.0, 0.0]          # ... of which chunks that went through the operator graph applied themselves
+
+    def begin_step(self):
+        self.sums = [0.0, 0.0, 0.0]
+        self.in_graph = [0.0, 0.0, 0.0]
+
+    def pending(self):
+        """the shares the step's own launch still has to apply"""
+        return [s_ - g_ for s_, g_ in zip(self.sums, self.in_graph)]
+
+    def _decay(self, w):
+        mine = w
+        for q in range(self.world_size):
+            w *= self.lr_factor
+            if q == self.rank:
+                mine = w
+        return mine, w
+
+    def chunk(self, lbatch, in_graph=False):
+        """a chunk has reached the loss -> its (density, appearance, bg) weights; their share w / lbatch is added to `sums` (and to
+        `in_graph` when the chunk adds the term to its own loss)"""
+        wd = wa = 0.0
+        if self.density > 0:
+            wd, self.density = self._decay(self.density)
+        if self.app > 0:
+            wa, self.app = self._decay(self.app)
+        wb = self.bg if self.bg > 0 else 0.0
+        for i, w in enumerate((wd, wa, wb)):
+            self.sums[i] += w / lbatch
+            if in_graph:
+                self.in_graph[i] += w / lbatch
+        return wd, wa, wb
+
+
+def tv_table(nerf, sd, sa, sb):
+    """(tensors, kinds, weights) of sd * TV_loss_density + sa * TV_loss_app + sb * bg_module.tv_loss(): the per-tensor factors 1e-2
+    (planes) and 1e-3 (lines) of fields/tensoRF.py:342-360; a term of weight 0 and a frozen parameter are left out.  Shapes are
+    read from the parameters as they are now (an upsample changes them)."""
+    ts, kinds, ws = [], [], []
+    for s_, f in ((sd, nerf.rf.density_rf), (sa, nerf.rf.app_rf)):
+        if s_ > 0:
+            for i in range(3):
+                ts += [f.app_plane[i], f.app_line[i]]
+                kinds += ["plane", "line"]
+                ws += [s_ * 1e-2, s_ * 1e-3]
+    if sb > 0 and nerf.bg_module is not None:
+        ts.append(nerf.bg_module.bg_mat)
+        kinds.append("env")
+        ws.append(sb)
+    keep = [i for i, t in enumerate(ts) if t.requires_grad]
+    return [ts[i] for i in keep], [kinds[i] for i in keep], [ws[i] for i in keep]
+
+
 class Trainer:
-    def __init__(self, nerf, params, world_size=1, rank=0, tape_free=True, check_every=None):
-        self.nerf = nerf
-        self.p = params
-        self.world_size, self.rank = world_size, rank
-        # The loss of microfacet_tensorf2.yaml:196-232: photometric + density_L1 + orientation + accumulated opacity.  The terms that
-        # file gives weight 0 are not assembled here -- a run that switches one on must not train silently without it.
-        on = [k for k in ("TV_weight_density", "TV_weight_app", "TV_weight_bg", "envmap_lambda", "diffuse_lambda", "brdf_lambda",
-                          "normal_err_lambda", "distortion_lambda", "visibility_lambda", "ortho_weight") if params.get(k)]
+    # loss terms of train.py that this step does not assemble (weight 0 in microfacet_tensorf2.yaml)
+    NOT_ASSEMBLED = ("envmap_lambda", "diffuse_lambda", "brdf_lambda", "normal_err_lambda", "distortion_lambda", "visibility_lambda",
+                     "ortho_weight")
+
+    @classmethod
+    def check_loss_terms(cls, params):
+        """a run that switches on a term this step does not assemble must not train silently without it"""
+        on = [k for k in cls.NOT_ASSEMBLED if params.get(k)]
         if on or params.get("charbonier_loss"):
             raise NotImplementedError(f"Trainer.step does not assemble the loss terms {on or ['charbonier_loss']} (weight 0 in "
                                       "microfacet_tensorf2.yaml); the reference-style loop over TensorNeRF.forward with "
                                       "nerf.regulariser_stats = True evaluates envmap_reg / brdf_reg / diffuse_reg")
+
+    def __init__(self, nerf, params, world_size=1, rank=0, tape_free=True, check_every=None, lr_decay_iters=-1,
+                 lr_decay_target_ratio=0.1):
+        self.nerf = nerf
+        self.p = params
+        self.world_size, self.rank = world_size, rank
+        # The loss of microfacet_tensorf2.yaml:196-232: photometric + density_L1 + orientation + accumulated opacity, and the three
+        # total-variation terms of train.py:684-709 when their weights are set (TVSchedule).
+        self.check_loss_terms(params)
+        self.tv = TVSchedule(params, lr_decay_iters, lr_decay_target_ratio, world_size, rank)
+        self.last_tv = None                              # the last step's weighted TV value (0-d device tensor; None: no TV term)
         self.batch = RayBatchController(params)          # train.py:504-507,618-626 (num_rays / lbatch_size)
         self.iteration = 0
         self.reduce = None
@@ -610,6 +692,14 @@ class Trainer:
                                          for q in g["params"] if id(q) not in dead])
 
     @property
+    def tv_weight_density(self):
+        return self.tv.density
+
+    @property
+    def tv_weight_app(self):
+        return self.tv.app
+
+    @property
     def num_rays(self):
         return self.batch.num_rays
 
@@ -641,6 +731,10 @@ class Trainer:
         pos, used_rays, losses, n_samples_last, n_chunks = 0, 0, [], None, 0
         went_graph = False
         bg = None
+        tv = self.tv if self.tv.on else None             # (weights all 0: nothing of the TV path is touched)
+        tv_vals, tv_env_done = [], False
+        if tv is not None:
+            tv.begin_step()
         fast = self.fast if (self.fast is not None and self.fast.supported()) else None
         if fast is not None:
             fast.begin_step()
@@ -654,15 +748,24 @@ class Trainer:
                 comm = fast._side["comm"] = torch.cuda.Stream()
             dev_ = rays.device
             def start_early(behind_chunks=False):
+                nonlocal tv_env_done
                 # What the collective reads must be complete and ordered in front of it: the zero fill of accumulators opened here (a rank
                 # whose chunks never reached the backward) and the env-map table gradient when the last chunk's backward did not queue
                 # it (that chunk kept no sample / left the fused pass / NMF_OVERLAP=0) while earlier chunks looked the map up -- both are
                 # queued on the current stream by prepare_early, and the communication stream then waits for it.
-                if fast.prepare_early(dev_, behind_chunks) or behind_chunks:
+                queued = fast.prepare_early(dev_, behind_chunks)
+                if tv is not None and tv.pending()[2] > 0.0:
+                    # the env map's TV share of this rank's chunks is in d_bg BEFORE the collective reads it (the bucket of such a step
+                    # starts behind the chunks, when the number of chunks that reached the loss is known)
+                    tv_vals.append(fast.add_env_tv(dev_, tv.pending()[2]))
+                    tv_env_done = queued = True
+                if queued or behind_chunks:
                     comm.wait_stream(torch.cuda.current_stream())
                 pairs = fast.early_pairs(dev_)
                 self.reduce.early_inplace(fast.comm_regions()[0], pairs, comm)
             early = (start_early, comm.cuda_stream)
+        # with TV_weight_bg the early bucket starts behind the chunks (below): the chunks' backwards get no callback
+        early_in_chunk = early if (tv is None or tv.bg <= 0) else None
         while pos < n_total:
             chunk = fixed_chunk if fixed_chunk is not None else max(int(self.num_rays), 1)
             if fetch is not None:
@@ -680,7 +783,7 @@ class Trainer:
                 try:
                     out = fast.chunk(r, gt, focal, noise, 1.0 / lbatch,
                                      (1.0, p["L1_weight_initial"], self.ori_lambda, 2.0 * self.pred_lambda),
-                                     want_total=trace is not None, last=pos >= n_total, early=early,
+                                     want_total=trace is not None, last=pos >= n_total, early=early_in_chunk,
                                      ctx=(n_chunks - 1) % fast.n_contexts)      # chunk k + 1's forward next to chunk k's backward
                 except Unsupported:
                     out = None                      # this chunk goes through the autograd path below
@@ -695,6 +798,8 @@ class Trainer:
                     used_rays += out["kept"]
                     losses.append(out["loss"])
                     n_samples_last = n_samples
+                    if tv is not None:
+                        tv.chunk(lbatch)                 # (the term itself: once per step, behind end_step)
                     if update_controllers:
                         self.batch.update(out["kept"], n_samples[0])
                         nerf.model.update_n_samples(n_samples[1:])
@@ -716,6 +821,12 @@ class Trainer:
                 terms.append(st["acc_terms"]); wts.append(2.0 * self.pred_lambda)
             else:
                 terms.append(st["prediction_loss"]); wts.append(self.pred_lambda)
+            if tv is not None:                                                                   # train.py:684-707
+                wd, wa, wb = tv.chunk(lbatch, in_graph=True)     # (this chunk's share goes through its graph, not the step's launch)
+                tab = tv_table(nerf, wd, wa, wb)
+                if tab[0]:
+                    terms.append(TVWeighted.apply(tuple(tab[1]), tuple(tab[2]), *tab[0])); wts.append(1.0)
+                    tv_vals.append(terms[-1].detach() / lbatch)
             total = LossMix.apply(1.0 / lbatch, wts, *terms)
             # train.py:704-705 skips a chunk whose loss is NaN (a host read-back per chunk); here the chunk is
             # back-propagated regardless and the optimizer launch is gated by the step's summed loss on the device (below)
@@ -737,6 +848,14 @@ class Trainer:
             self.reduce.finish_early()            # the sums are in the accumulator tensors before end_step turns them into .grad
         if fast is not None:
             fast.end_step()
+        if tv is not None:
+            pend = tv.pending()
+            if fast is not None and max(pend) > 0.0:
+                # ONE launch for the step: value + gradient of every TV term, added to the gradients end_step has just handed over
+                tab = tv_table(nerf, pend[0], pend[1], 0.0 if tv_env_done else pend[2])
+                if tab[0]:
+                    tv_vals.append(fast.add_tv(*tab))
+            self.last_tv = None if not tv_vals else (tv_vals[0] if len(tv_vals) == 1 else torch.stack(tv_vals).sum())
         # NaN guard (train.py:704-705 reads the loss back and skips a NaN chunk): the summed loss of the step stays on the
         # device and gates the fused Adam launch -- a non-finite loss leaves parameters and moments untouched, no host sync.
         # With several ranks the value that gates is the SUM of the ranks' guards (it rides in the gradient all-reduce): a
@@ -775,7 +894,7 @@ class Trainer:
         if pre is not None:
             pre.prefetch()            # next step's derived tables, on a side stream behind this optimizer update
         return StepStats(losses, rays=used_rays, n_samples=n_samples_last, comm_bytes=comm_bytes, chunks=n_chunks,
-                         reduce=self.reduce)
+                         reduce=self.reduce, **({} if tv is None else {"tv_dev": self.last_tv}))
 
 
 class StepStats(dict):
@@ -794,9 +913,15 @@ class StepStats(dict):
         if key == "comm_exposed_ms":     # time the main stream waited for the step's collectives (early remainder + late bucket)
             self[key] = self["reduce"].exposed_ms() if self.get("reduce") is not None and self["comm_bytes"] else None
             return self[key]
-        if key not in ("loss", "psnr"):
+        if key not in ("loss", "psnr", "tv"):
             raise KeyError(key)
-        vals = torch.stack(self._losses).tolist() if self._losses else []
+        tvd = self.get("tv_dev")
+        # (one read-back for the losses and the TV value: the reference's `TVs` log costs no synchronisation of its own)
+        if tvd is None:
+            vals = torch.stack(self._losses).tolist() if self._losses else []
+        else:
+            vals = torch.stack([v.float().reshape(()) for v in self._losses] + [tvd.float().reshape(())]).tolist()
+        self["tv"] = vals.pop() if tvd is not None else 0.0
         good = [v for v in vals if math.isfinite(v)]           # a chunk whose loss is not finite is left out of the statistics
         self["nan_chunks"] = len(vals) - len(good)
         loss_sum = float(sum(good))
