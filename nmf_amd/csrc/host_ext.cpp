@@ -4,8 +4,9 @@
 // costs 10-25 us of Python per call -- one torch.empty per output (~2 us each), a checked data_ptr per argument, ctypes
 // marshalling -- against 3-10 us of kernel time.  The functions here are THE implementation of the hip.py wrappers of the
 // same name (output allocation, argument checks, the C-ABI entry point of include/nmf_hip.h -- with the compiler checking
-// the prototypes), in ~3 us.  hip.py loads this module at import and raises without it; each wrapper there is one call into
-// it (a few keep a ctypes path for the argument forms not covered here: bf16 tables, out=None, ...).
+// the prototypes), in ~3 us.  hip.py loads this module at import and raises without it.  The rule: a hip.py wrapper uses
+// ctypes only if this file has no function for that entry point; every argument form of an entry point that is wrapped
+// here (bf16 tables, out=, l1=, absent bounce rows, ...) goes through the one function here, which StepCore calls too.
 #include <torch/extension.h>
 
 #include <algorithm>
@@ -58,6 +59,11 @@ void* vptr(const OT& t) {
     if (!t->is_cuda()) fail("nmf_amd operators need device tensors (no CPU path)");
     if (!t->is_contiguous()) fail("tensor must be contiguous");
     return t->data_ptr();
+}
+const float* dense_f32(const Tensor& t) {       // hip._dense_f32: contiguous or channels-last storage
+    if (t.scalar_type() != at::kFloat || !t.is_cuda()) fail("expected a float32 device tensor");
+    if (!(t.is_contiguous() || t.is_contiguous(at::MemoryFormat::ChannelsLast))) fail("tensor storage must be dense");
+    return static_cast<const float*>(t.data_ptr());
 }
 const float* f32(const Tensor& t) { return ptr<const float>(t, at::kFloat); }
 const float* of32(const OT& t) { return optr<const float>(t, at::kFloat); }
@@ -231,11 +237,12 @@ std::tuple<OT, OT, OT, OT, OT, OT> vm_query_fwd(int64_t p_addr, const Tensor& xy
     }
     if (bf16) {        // bfloat16 copies of the tables (BASELINE configs[1]); fp32 arithmetic
         const uint16_t *a[3], *b[3], *c[3], *d[3];
+        auto h = [](const Tensor& t) { return ptr<const uint16_t>(t, at::kBFloat16); };
         for (int i = 0; i < 3; ++i) {
-            a[i] = need_d ? static_cast<const uint16_t*>(vptr(dpk.at(i))) : nullptr;
-            b[i] = need_d ? static_cast<const uint16_t*>(vptr(dlk.at(i))) : nullptr;
-            c[i] = need_a ? static_cast<const uint16_t*>(vptr(apl.at(i))) : nullptr;
-            d[i] = need_a ? static_cast<const uint16_t*>(vptr(ali.at(i))) : nullptr;
+            a[i] = need_d ? h(dpk.at(i)) : nullptr;
+            b[i] = need_d ? h(dlk.at(i)) : nullptr;
+            c[i] = need_a ? h(apl.at(i)) : nullptr;
+            d[i] = need_a ? h(ali.at(i)) : nullptr;
         }
         check(nmf_vm_query_fwd_bf16(p, f32(xyzt), M, need_d ? a : nullptr, need_d ? b : nullptr, need_a ? c : nullptr,
                                     need_a ? d : nullptr, need_a ? of32(basis) : nullptr, o(sf), o(sg), o(gr), o(nr), o(ap), o(cf),
@@ -362,16 +369,19 @@ Tensor brdf_mlp_pack(const std::vector<Tensor>& w, const OT& into, int64_t strea
 // ---- material maps of the evaluation pass (nmf_material_maps) -----------------------------------------------------------
 // -> [B,15]: albedo | roughness | diffuse | tint | spec, 3 columns each
 Tensor material_maps(const Tensor& app, const Tensor& normals, const Tensor& w, const Tensor& offsets, const Tensor& rays,
-                     const Tensor& W, const Tensor& b, const std::vector<double>& hp, const Tensor& conv, const Tensor& inv,
-                     const Tensor& row_off, const Tensor& cnt, const Tensor& incoming, const Tensor& brdf_weight, const Tensor& acc,
+                     const Tensor& W, const Tensor& b, const std::vector<double>& hp, const Tensor& conv, const OT& inv,
+                     const OT& row_off, const OT& cnt, const OT& incoming, const OT& brdf_weight, const Tensor& acc,
                      const Tensor& bg, int64_t stream) {
+    // inv / row_off / cnt / incoming / brdf_weight all absent: no bounce row (Mb = R = 0), tint and spec are 0
     TimedScope _ts(__func__, stream);
     if (hp.size() != 5) fail("material_maps: hp = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)");
-    const int64_t B = offsets.size(0) - 1, M = app.size(0), Mb = row_off.size(0) - 1, R = incoming.size(0);
+    const int64_t B = offsets.size(0) - 1, M = app.size(0);
+    const int64_t Mb = row_off.has_value() ? row_off->size(0) - 1 : 0, R = incoming.has_value() ? incoming->size(0) : 0;
     Tensor o = fe(app, {B, 15});
     check(nmf_material_maps(f32(app), f32(normals), f32(w), i64(offsets), B, M, f32(rays), f32(W), f32(b), (float)hp[0], (float)hp[1],
-                            (float)hp[2], (float)hp[3], (float)hp[4], f32(conv), i32(inv), i64(row_off), i32(cnt), Mb, f32(incoming),
-                            f32(brdf_weight), R, f32(acc), f32(bg), out(o), st(stream)),
+                            (float)hp[2], (float)hp[3], (float)hp[4], f32(conv), optr<const int32_t>(inv, at::kInt),
+                            optr<const int64_t>(row_off, at::kLong), optr<const int32_t>(cnt, at::kInt), Mb, of32(incoming),
+                            of32(brdf_weight), R, f32(acc), f32(bg), out(o), st(stream)),
           "nmf_material_maps");
     return o;
 }
@@ -847,23 +857,50 @@ void vm_query_bwd_planned(int64_t p_addr, const std::vector<Seg>& segs, const st
     vm_query_bwd_impl(__func__, p_addr, segs, dpk, dlk, apl, ali, basis, g_dpk, g_dlk, g_apl, g_ali, g_basis, OT(plan), stream);
 }
 
-std::tuple<std::vector<Tensor>, std::vector<Tensor>> vm_unpack_density_grad(int64_t p_addr, const std::vector<Tensor>& g_dpk,
-                                                                            const std::vector<Tensor>& g_dlk, int64_t stream) {
+// out: the (gp, gl) of an earlier call, overwritten; l1: (the six density parameters in the gradients' storage order, 0-d device
+// scale) -- the gradient of scale * sum_i mean |x_i| is added in the same launch (nmf_vm_unpack_density_grad_l1)
+using Lists2 = std::tuple<std::vector<Tensor>, std::vector<Tensor>>;
+Lists2 vm_unpack_density_grad(int64_t p_addr, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
+                              const c10::optional<Lists2>& into, const c10::optional<std::tuple<std::vector<Tensor>, Tensor>>& l1,
+                              int64_t stream) {
     TimedScope _ts(__func__, stream);
     const auto* p = reinterpret_cast<const nmf_vm_params*>(p_addr);
     const int64_t G = p->grid;
     P3 a = three(g_dpk), b = three(g_dlk);
     std::vector<Tensor> gp, gl;
+    if (into.has_value()) {
+        gp = std::get<0>(*into);
+        gl = std::get<1>(*into);
+        if (gp.size() != 3 || gl.size() != 3) fail("vm_unpack_density_grad: out = (three plane gradients, three line gradients)");
+    }
     float *op[3], *ol[3];
     for (int i = 0; i < 3; ++i) {
-        // parameter-shaped ([1,16,G,G] / [1,16,G,1]) with channel-last strides: the storage is the [G][G][16] / [G][16] the
-        // kernel writes, and autograd gets the gradient without a chain of permute / unsqueeze views
-        gp.push_back(at::empty({1, 16, G, G}, g_dpk[0].options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast)));
-        gl.push_back(at::empty({1, 16, G, 1}, g_dpk[0].options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast)));
-        op[i] = out(gp[i]);
-        ol[i] = out(gl[i]);
+        if (!into.has_value()) {
+            // parameter-shaped ([1,16,G,G] / [1,16,G,1]) with channel-last strides: the storage is the [G][G][16] / [G][16] the
+            // kernel writes, and autograd gets the gradient without a chain of permute / unsqueeze views
+            gp.push_back(at::empty({1, 16, G, G}, g_dpk[0].options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast)));
+            gl.push_back(at::empty({1, 16, G, 1}, g_dpk[0].options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast)));
+        } else if (gp[i].numel() != 16 * G * G || gl[i].numel() != 16 * G) {
+            fail("vm_unpack_density_grad: out holds [G,G,16] plane and [G,16] line gradients");
+        }
+        op[i] = const_cast<float*>(dense_f32(gp[i]));
+        ol[i] = const_cast<float*>(dense_f32(gl[i]));
     }
-    check(nmf_vm_unpack_density_grad(p, a.p, b.p, op, ol, st(stream)), "nmf_vm_unpack_density_grad");
+    if (l1.has_value()) {
+        const std::vector<Tensor>& xs = std::get<0>(*l1);
+        if (xs.size() != 6) fail("vm_unpack_density_grad: l1 = (six density parameters, scale)");
+        const float *xp[3], *xl[3];
+        for (int i = 0; i < 3; ++i) {
+            if (xs[i].numel() != gp[i].numel() || xs[3 + i].numel() != gl[i].numel())
+                fail("vm_unpack_density_grad: parameter / gradient size mismatch");
+            xp[i] = dense_f32(xs[i]);
+            xl[i] = dense_f32(xs[3 + i]);
+        }
+        check(nmf_vm_unpack_density_grad_l1(p, a.p, b.p, op, ol, xp, xl, f32(std::get<1>(*l1)), st(stream)),
+              "nmf_vm_unpack_density_grad_l1");
+    } else {
+        check(nmf_vm_unpack_density_grad(p, a.p, b.p, op, ol, st(stream)), "nmf_vm_unpack_density_grad");
+    }
     return {gp, gl};
 }
 
@@ -1042,12 +1079,6 @@ void multi_copy(int64_t slots_addr, int64_t n, int64_t stream) {
     check(nmf_multi_copy(reinterpret_cast<const nmf_copy_slot*>(slots_addr), (int32_t)n, st(stream)), "nmf_multi_copy");
 }
 
-const float* dense_f32(const Tensor& t) {       // hip._dense_f32: contiguous or channels-last storage
-    if (t.scalar_type() != at::kFloat || !t.is_cuda()) fail("expected a float32 device tensor");
-    if (!(t.is_contiguous() || t.is_contiguous(at::MemoryFormat::ChannelsLast))) fail("tensor storage must be dense");
-    return static_cast<const float*>(t.data_ptr());
-}
-
 std::vector<Tensor> loss_mix_bwd(const std::vector<std::vector<int64_t>>& shapes, const std::vector<double>& weights,
                                  double scale, const Tensor& d_out, int64_t stream) {
     TimedScope _ts(__func__, stream);
@@ -1067,7 +1098,9 @@ std::vector<Tensor> loss_mix_bwd(const std::vector<std::vector<int64_t>>& shapes
     return grads;
 }
 
-void l1_mean_bwd_into(const std::vector<Tensor>& tensors, const Tensor& d_out, std::vector<Tensor> grads, int64_t stream) {
+// accumulate: the gradients are added to `grads`; otherwise `grads` is overwritten (fresh tensors of the allocating form)
+void l1_mean_bwd_into(const std::vector<Tensor>& tensors, const Tensor& d_out, std::vector<Tensor> grads, bool accumulate,
+                      int64_t stream) {
     TimedScope _ts(__func__, stream);
     const size_t n = tensors.size();
     if (grads.size() != n || n > 32) fail("l1_mean_bwd: tensors / gradients");
@@ -1080,7 +1113,7 @@ void l1_mean_bwd_into(const std::vector<Tensor>& tensors, const Tensor& d_out, s
         g[i] = const_cast<float*>(dense_f32(grads[i]));
         numel[i] = tensors[i].numel();
     }
-    check(nmf_l1_mean_bwd(x, numel, (int32_t)n, f32(d_out), g, 1, st(stream)), "nmf_l1_mean_bwd");
+    check(nmf_l1_mean_bwd(x, numel, (int32_t)n, f32(d_out), g, accumulate ? 1 : 0, st(stream)), "nmf_l1_mean_bwd");
 }
 
 void sat_build_bwd_into(Tensor d_sat, const Tensor& bg, const Tensor& act, const OT& d_pole, double brightness, double mul,
@@ -1221,10 +1254,12 @@ PYBIND11_MODULE(_nmf_host, m) {
     m.def("march_count", &march_count);
     m.def("march_scan", &march_scan, py::arg("counts"), py::arg("max_samples"), py::arg("stream"), py::arg("pub") = 0, py::arg("pub_seq") = 0);
     m.def("march_fill", &march_fill);
-    m.def("vm_query_fwd", [](int64_t p_addr, const Tensor& xyzt, const std::vector<Tensor>& dpk, const std::vector<Tensor>& dlk,
-                             const std::vector<Tensor>& apl, const std::vector<Tensor>& ali, const OT& basis, bool want_density,
-                             bool want_normal, bool want_app, bool want_coef, int64_t stream) {
-        return vm_query_fwd(p_addr, xyzt, dpk, dlk, apl, ali, basis, want_density, want_normal, want_app, want_coef, stream, 0);
+    using OV = c10::optional<std::vector<Tensor>>;          // None for the tables of the half that is not asked for
+    m.def("vm_query_fwd", [](int64_t p_addr, const Tensor& xyzt, const OV& dpk, const OV& dlk, const OV& apl, const OV& ali, const OT& basis,
+                             bool want_density, bool want_normal, bool want_app, bool want_coef, int64_t stream) {
+        const std::vector<Tensor> none;
+        return vm_query_fwd(p_addr, xyzt, dpk ? *dpk : none, dlk ? *dlk : none, apl ? *apl : none, ali ? *ali : none, basis,
+                            want_density, want_normal, want_app, want_coef, stream, 0);
     });
     m.def("composite_fwd", &composite_fwd);
     m.def("segment_sum", &segment_sum);

@@ -3,10 +3,12 @@ classes reach the GPU kernels; there is no CPU or PyTorch fallback: if a library
 import of any product operator raises.
 
 torch is used for what it is here for: device memory (tensors), the current HIP stream and
-torch.distributed.  Every wrapper takes torch tensors, checks dtype / contiguity / device and
-passes raw pointers + sizes + the current stream to the C ABI.  Each wrapper has ONE implementation:
-the per-step ones call lib/_nmf_host.so (csrc/host_ext.cpp: output allocation, checks and the
-C-ABI call in C++, ~3 us per call instead of 10-25 us of Python), the others go through ctypes.
+torch.distributed.  Every wrapper takes torch tensors and has ONE implementation.  The rule: a wrapper
+uses ctypes only if csrc/host_ext.cpp has no function for that entry point.  Where it has one, the wrapper
+is one call into lib/_nmf_host.so for every argument form (output allocation, dtype / contiguity / device
+checks and the C-ABI call in C++, ~3 us per call instead of 10-25 us of Python, and the code the fused
+step runs); an allocating form at most allocates its outputs and calls the `*_into` function.  The ctypes
+wrappers (off the per-step path) check the tensors and pass raw pointers + sizes + the current stream.
 """
 import ctypes as C
 import importlib.util
@@ -51,9 +53,6 @@ def _load_host():
 
 _lib = _load()
 HOST_EXT = _load_host()
-
-c_f32p = C.POINTER(C.c_float)
-c_vp = C.c_void_p
 
 
 class MarchParams(C.Structure):
@@ -138,21 +137,6 @@ def _declare_from_header():
 
 
 _declare_from_header()
-_lib.nmf_last_error_string.restype = C.c_char_p
-_lib.nmf_version.restype = C.c_int
-_lib.nmf_vm_bwd_workspace_bytes.restype = C.c_int64
-_lib.nmf_vm_bin_plan_bytes.restype = C.c_int64
-_lib.nmf_vm_walk_workspace_bytes.restype = C.c_int64
-_lib.nmf_march_scan_workspace_bytes.restype = C.c_int64
-_lib.nmf_bounce_index_workspace_bytes.restype = C.c_int64
-_lib.nmf_argsort_workspace_bytes.restype = C.c_int64
-_lib.nmf_topk_select_workspace_bytes.restype = C.c_int64
-_lib.nmf_alpha_coarse_words.restype = C.c_int64
-_lib.nmf_sat_lookup_bwd_workspace_bytes.restype = C.c_int64
-_lib.nmf_ssim_workspace_bytes.restype = C.c_int64
-_lib.nmf_normal_err_workspace_bytes.restype = C.c_int64
-_lib.nmf_mc_workspace_bytes.restype = C.c_int64
-_lib.nmf_tv_workspace_bytes.restype = C.c_int64
 
 
 def version():
@@ -342,46 +326,20 @@ def vm_params(aabb, inv_size, density_shift, grid):
 
 def vm_pack_density(p, planes, lines, out=None):
     """planes[i]: [G,G,16] channel-last storage, lines[i]: [G,16].  out = (dpk, dlk) of an earlier call re-packs in place."""
-    if out is not None:
-        HOST_EXT.vm_pack_density_into(C.addressof(p), list(planes), list(lines), list(out[0]), list(out[1]), _stream())
-        return out
-    G = p.grid
-    dev = planes[0].device
-    dpk = [torch.empty((G, G, 48), dtype=torch.float32, device=dev) for _ in range(3)]
-    dlk = [torch.empty((G, 32), dtype=torch.float32, device=dev) for _ in range(3)]
-    _check(_lib.nmf_vm_pack_density(C.byref(p), _p3(planes), _p3(lines), _p3(dpk), _p3(dlk), _stream()),
-           "nmf_vm_pack_density")
-    return dpk, dlk
+    if out is None:
+        G, dev = p.grid, planes[0].device
+        out = ([torch.empty((G, G, 48), dtype=torch.float32, device=dev) for _ in range(3)],
+               [torch.empty((G, 32), dtype=torch.float32, device=dev) for _ in range(3)])
+    HOST_EXT.vm_pack_density_into(C.addressof(p), list(planes), list(lines), list(out[0]), list(out[1]), _stream())
+    return out
 
 
 def vm_query_fwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, want_density=True, want_normal=True,
                  want_app=True, want_coef=False):
-    """-> (sigma_feat [M], sigma [M], grad [M,3], normal [M,3], app [M,24], coef [M,72]); None for what is not asked for"""
-    if app_planes[0].dtype == torch.float32:
-        return HOST_EXT.vm_query_fwd(C.addressof(p), xyzt, dpk, dlk, app_planes, app_lines, basis, want_density, want_normal,
-                                     want_app, want_coef, _stream())
-    # bf16 tables: this ctypes path dispatches on the table dtype
-    M = xyzt.shape[0]
-    dev = xyzt.device
-    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
-    sf = f(M) if want_density else None
-    sg = f(M) if want_density else None
-    gr = f(M, 3) if want_normal else None
-    nr = f(M, 3) if want_normal else None
-    ap = f(M, 24) if want_app else None
-    cf = f(M, 72) if want_coef else None
-    need_d = want_density or want_normal
-    need_a = want_app or want_coef
-    probe = dpk[0] if (need_d and dpk is not None) else app_planes[0]
-    if probe.dtype == torch.bfloat16:          # bf16-table variant: same kernel, half the bytes per tap
-        fn, name, td = _lib.nmf_vm_query_fwd_bf16, "nmf_vm_query_fwd_bf16", torch.bfloat16
-    else:
-        fn, name, td = _lib.nmf_vm_query_fwd, "nmf_vm_query_fwd", torch.float32
-    _check(fn(C.byref(p), _p(xyzt, torch.float32), C.c_int64(M),
-              _p3(dpk, td) if need_d else None, _p3(dlk, td) if need_d else None,
-              _p3(app_planes, td) if need_a else None, _p3(app_lines, td) if need_a else None,
-              _p(basis) if need_a else None, _p(sf), _p(sg), _p(gr), _p(nr), _p(ap), _p(cf), _stream()), name)
-    return sf, sg, gr, nr, ap, cf
+    """-> (sigma_feat [M], sigma [M], grad [M,3], normal [M,3], app [M,24], coef [M,72]); None for what is not asked for.  The tables
+    are fp32 or bfloat16 (the dtype of the first table the query needs decides)"""
+    return HOST_EXT.vm_query_fwd(C.addressof(p), xyzt, dpk, dlk, app_planes, app_lines, basis, want_density, want_normal,
+                                 want_app, want_coef, _stream())
 
 
 def vm_query_rows(p, xyzt, dpk, dlk):
@@ -435,16 +393,7 @@ def vm_bin_plan(p, xyzts):
     """The brick sort of a backward walk over the sample sets `xyzts` ([M_i,4] each), from the positions alone -> opaque plan
     tensor for vm_query_bwd_segments(..., plan=) over the same sets in the same order (a training pass builds it under its
     forward; the backward then only permutes the adjoints)."""
-    n = len(xyzts)
-    if n == 0 or n > VM_MAX_SEGMENTS:
-        raise NmfHipError(f"1..{VM_MAX_SEGMENTS} segments per plan")
-    ptrs = (C.c_void_p * n)(*[_p(x, torch.float32) for x in xyzts])
-    Ms = (C.c_int64 * n)(*[int(x.shape[0]) for x in xyzts])
-    M = sum(int(x.shape[0]) for x in xyzts)
-    nbytes = _lib.nmf_vm_bin_plan_bytes(C.c_int64(M), C.c_int32(p.grid))
-    plan = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=xyzts[0].device)
-    _check(_lib.nmf_vm_bin_plan(C.byref(p), ptrs, Ms, C.c_int32(n), _p(plan), C.c_int64(nbytes), _stream()), "nmf_vm_bin_plan")
-    return plan
+    return HOST_EXT.vm_bin_plan(C.addressof(p), list(xyzts), _stream())
 
 
 def vm_bwd_clean_scratch(p, device):
@@ -469,32 +418,7 @@ def vm_unpack_density_grad(p, g_dpk, g_dlk, out=None, l1=None):
     """out = (gp, gl) of an earlier call: the same tensors are overwritten (a training pass keeps its gradient tensors).
     l1 = (the six density parameters [planes + lines] in the gradients' storage order, 0-d device scale): the gradient of
     scale * sum_i mean |x_i| is added in the same launch (same bits as l1_mean_bwd(..., out=gp + gl) behind the unpack)"""
-    if out is None and l1 is None:
-        return HOST_EXT.vm_unpack_density_grad(C.addressof(p), g_dpk, g_dlk, _stream())
-    G = p.grid
-    dev = g_dpk[0].device
-    if out is not None:
-        gp, gl = out
-    else:
-        # parameter-shaped outputs with channel-last strides: the storage is the [G][G][16] / [G][16] the kernel writes
-        gp = [torch.empty((1, 16, G, G), dtype=torch.float32, device=dev).contiguous(memory_format=torch.channels_last)
-              for _ in range(3)]
-        gl = [torch.empty((1, 16, G, 1), dtype=torch.float32, device=dev).contiguous(memory_format=torch.channels_last)
-              for _ in range(3)]
-    arr_p, arr_l = (C.c_void_p * 3)(*[t.data_ptr() for t in gp]), (C.c_void_p * 3)(*[t.data_ptr() for t in gl])
-    if l1 is not None:
-        xs, scale = l1
-        for x, g in zip(xs, gp + gl):
-            if x.numel() != g.numel():
-                raise NmfHipError("vm_unpack_density_grad: parameter / gradient size mismatch")
-        xp = (C.c_void_p * 3)(*[_dense_f32(t) for t in xs[:3]])
-        xl = (C.c_void_p * 3)(*[_dense_f32(t) for t in xs[3:]])
-        _check(_lib.nmf_vm_unpack_density_grad_l1(C.byref(p), _p3(g_dpk), _p3(g_dlk), arr_p, arr_l, xp, xl, _p(scale, torch.float32),
-                                                  _stream()), "nmf_vm_unpack_density_grad_l1")
-        return gp, gl
-    _check(_lib.nmf_vm_unpack_density_grad(C.byref(p), _p3(g_dpk), _p3(g_dlk), arr_p, arr_l, _stream()),
-           "nmf_vm_unpack_density_grad")
-    return gp, gl
+    return HOST_EXT.vm_unpack_density_grad(C.addressof(p), g_dpk, g_dlk, out, l1, _stream())
 
 
 # ---- compositing --------------------------------------------------------------------------------
@@ -519,24 +443,15 @@ def sat_build(bg_mat, brightness=0.0, mul=1.0, sc=None, out=None, pole=False, in
     interleaved copy of sat [H,W,4] with interleaved=True: what the lookups read fastest).  sc: optional device float32 [3] =
     (mipbias, brightness, mul) read by the kernels instead of the by-value scalars (no host read-back of the parameters).
     out = the tuple of an earlier call (same flags) rebuilds the tables in place."""
-    if out is not None and bg_mat.is_contiguous():
-        HOST_EXT.sat_build_into(bg_mat, float(brightness), float(mul), sc, out[0], out[1], out[2] if pole else None,
-                                out[-1] if interleaved else None, _stream())
-        return (out[0], out[1]) + ((out[2],) if pole else ()) + ((out[-1],) if interleaved else ())
-    bg = bg_mat.reshape(3, bg_mat.shape[-2], bg_mat.shape[-1])
-    H, W = bg.shape[-2:]
-    if out is not None:
-        act, sat = out[0], out[1]
-        pl = out[2] if pole else None
-        s4 = out[-1] if interleaved else None
-    else:
-        act = torch.empty_like(bg)
-        sat = torch.empty_like(bg)
-        pl = torch.empty((2, 3), dtype=torch.float32, device=bg.device) if pole else None
-        s4 = torch.zeros((H, W, 4), dtype=torch.float32, device=bg.device) if interleaved else None
-    _check(_lib.nmf_sat_build(_p(bg.contiguous(), torch.float32), C.c_int32(H), C.c_int32(W), C.c_float(brightness),
-                              C.c_float(mul), _p(sc), _p(act), _p(sat), _p(pl), _p(s4), _stream()), "nmf_sat_build")
-    return (act, sat) + ((pl,) if pole else ()) + ((s4,) if interleaved else ())
+    bg = bg_mat.reshape(3, bg_mat.shape[-2], bg_mat.shape[-1]).contiguous()
+    if out is None:
+        H, W = bg.shape[-2:]
+        out = ((torch.empty_like(bg), torch.empty_like(bg))
+               + ((torch.empty((2, 3), dtype=torch.float32, device=bg.device),) if pole else ())
+               + ((torch.zeros((H, W, 4), dtype=torch.float32, device=bg.device),) if interleaved else ()))     # channel 3 is never written
+    HOST_EXT.sat_build_into(bg, float(brightness), float(mul), sc, out[0], out[1], out[2] if pole else None,
+                            out[-1] if interleaved else None, _stream())
+    return (out[0], out[1]) + ((out[2],) if pole else ()) + ((out[-1],) if interleaved else ())
 
 
 def _sat_layout(sat):
@@ -548,29 +463,21 @@ def _sat_layout(sat):
 
 def sh_project(vals, wq, sh_A, out=None):
     """-> (coeffs [K,3], conv [K,3]); wq [n,K] contiguous, sh_A [>=K]"""
-    if out is not None:
-        HOST_EXT.sh_project_into(vals, wq, sh_A, out[0], out[1], _stream())
-        return out
-    n, K = wq.shape[0], wq.shape[1]
-    out = (torch.empty((K, 3), dtype=torch.float32, device=vals.device),
-           torch.empty((K, 3), dtype=torch.float32, device=vals.device))
-    _check(_lib.nmf_sh_project(_p(vals, torch.float32), _p(wq, torch.float32), C.c_int64(n), C.c_int32(K),
-                               _p(sh_A, torch.float32), _p(out[0]), _p(out[1]), _stream()), "nmf_sh_project")
+    if out is None:
+        K = wq.shape[1]
+        out = (torch.empty((K, 3), dtype=torch.float32, device=vals.device),
+               torch.empty((K, 3), dtype=torch.float32, device=vals.device))
+    HOST_EXT.sh_project_into(vals, wq, sh_A, out[0], out[1], _stream())
     return out
 
 
 def sat_build_bwd(d_sat, bg_mat, act, d_pole, brightness=0.0, mul=1.0, sc=None, out=None):
     """-> d_bg [3,H,W] (out: written in place)"""
-    if out is not None and bg_mat.is_contiguous():
-        HOST_EXT.sat_build_bwd_into(d_sat, bg_mat, act, d_pole, float(brightness), float(mul), sc, out, _stream())
-        return out
-    bg = bg_mat.reshape(3, bg_mat.shape[-2], bg_mat.shape[-1])
-    H, W = bg.shape[-2:]
-    d_bg = out if out is not None else torch.empty_like(bg)
-    _check(_lib.nmf_sat_build_bwd(_p(d_sat, torch.float32), _p(bg.contiguous(), torch.float32), _p(act), C.c_int32(H),
-                                  C.c_int32(W), C.c_float(brightness), C.c_float(mul), _p(sc), _p(d_pole), _p(d_bg), _stream()),
-           "nmf_sat_build_bwd")
-    return d_bg
+    bg = bg_mat.reshape(3, bg_mat.shape[-2], bg_mat.shape[-1]).contiguous()
+    if out is None:
+        out = torch.empty_like(bg)
+    HOST_EXT.sat_build_bwd_into(d_sat, bg, act, d_pole, float(brightness), float(mul), sc, out, _stream())
+    return out
 
 
 def sat_lookup_fwd(sat, dirs, sa, mipbias, pole_rows, sc=None):
@@ -589,38 +496,11 @@ def sat_lookup_fwd(sat, dirs, sa, mipbias, pole_rows, sc=None):
 ENV_BINNED_MIN_LOOKUPS = 30000
 
 
-def _cdiv(a, b):
-    return -(-a // b)
-
-
-def sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, want_dirs=True, want_mipbias=None, sc=None):
-    """d_sat [H,W,4] / d_pole [2,3] / d_mip [1] are ACCUMULATED into (any may be None except d_pole).  Returns d_dirs; with
-    want_mipbias=True (legacy form) a fresh d_mip accumulator is allocated and (d_dirs, d_mip) is returned."""
-    if want_mipbias is None:
-        return HOST_EXT.sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, sc,
-                                       int(ENV_BINNED_MIN_LOOKUPS), _stream())
-    # the legacy return form (tests)
-    R, ld = dirs.shape[0], dirs.shape[1]
-    H, W, layout = _sat_layout(sat)
-    d_dirs = torch.empty((R, ld), dtype=torch.float32, device=dirs.device) if want_dirs else None   # shaped like dirs
-    if want_mipbias and d_mip is None:
-        d_mip = torch.zeros(1, dtype=torch.float32, device=dirs.device)
-    if d_sat is not None and R >= ENV_BINNED_MIN_LOOKUPS and _cdiv(H, 32) * _cdiv(W, 64) <= 1024:
-        # many lookups: the binned table adjoint (csrc/env.hip).  The record pool comes from torch's stream-ordered caching
-        # allocator per call: two of these calls may be in flight on different streams (fast_step's side streams)
-        nbytes = int(_lib.nmf_sat_lookup_bwd_workspace_bytes(C.c_int64(R)))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dirs.device)
-        _check(_lib.nmf_sat_lookup_bwd_binned(_p(sat, torch.float32), C.c_int32(H), C.c_int32(W), _p(dirs, torch.float32),
-                                              C.c_int32(ld), _p(sa, torch.float32), C.c_int64(R), C.c_float(mipbias), _p(sc),
-                                              C.c_int32(layout), _p(d_out.contiguous(), torch.float32), _p(d_sat), _p(d_pole),
-                                              _p(d_dirs), _p(d_mip), _p(ws), C.c_int64(nbytes), _stream()),
-               "nmf_sat_lookup_bwd_binned")
-        return d_dirs, d_mip
-    _check(_lib.nmf_sat_lookup_bwd(_p(sat, torch.float32), C.c_int32(H), C.c_int32(W), _p(dirs, torch.float32),
-                                   C.c_int32(ld), _p(sa, torch.float32), C.c_int64(R), C.c_float(mipbias), _p(sc), C.c_int32(layout),
-                                   _p(d_out.contiguous(), torch.float32), _p(d_sat), _p(d_pole), _p(d_dirs), _p(d_mip),
-                                   _stream()), "nmf_sat_lookup_bwd")
-    return d_dirs, d_mip
+def sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, want_dirs=True, sc=None):
+    """d_sat [H,W,4] / d_pole [2,3] / d_mip [1] are ACCUMULATED into (any may be None except d_pole).  Returns d_dirs shaped like
+    dirs (None without want_dirs)."""
+    return HOST_EXT.sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, sc,
+                                   int(ENV_BINNED_MIN_LOOKUPS), _stream())
 
 
 # ---- shading helpers -------------------------------------------------------------------------------
@@ -688,36 +568,10 @@ def brdf_mlp_bwd(weights, half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_
                                  list(grads), int(max_workgroups), _stream(), image)
 
 
-class MlpBwdSegment(C.Structure):
-    _fields_ = [("half_vec", C.c_void_p), ("diff_vec", C.c_void_p), ("feat_src", C.c_void_p), ("rough_src", C.c_void_p),
-                ("src_idx", C.c_void_p), ("R", C.c_int64), ("fwd_out", C.c_void_p), ("act_mask", C.c_void_p), ("d_out", C.c_void_p),
-                ("d_feat", C.c_void_p)]
-
-
 def brdf_mlp_bwd_segments(weights, sets, grads, max_workgroups=0, image=None):
     """brdf_mlp_bwd over one or two ray sets in ONE launch (the evaluations of a level and of the level below share the weights).
     sets: tuples (half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_out, act_mask, d_out) -> list of d_feat, one per set."""
-    if not 1 <= len(sets) <= 2:
-        raise ValueError("brdf_mlp_bwd_segments: one or two ray sets")
-    dev = sets[0][0].device
-    arr = (MlpBwdSegment * len(sets))()
-    keep, outs = [], []
-    for i, (hv, dv, feat, rough, idx, out, mask, d_out) in enumerate(sets):
-        d_feat = torch.zeros((feat.shape[0], 24), dtype=torch.float32, device=dev)
-        go = d_out.contiguous()
-        keep.append(go)
-        outs.append(d_feat)
-        arr[i] = MlpBwdSegment(_p(hv, torch.float32), _p(dv, torch.float32), _p(feat, torch.float32), _p(rough, torch.float32),
-                               _p(idx, torch.int32), hv.shape[0], _p(out, torch.float32), _p(mask, torch.int32), _p(go, torch.float32),
-                               _p(d_feat))
-    Rs = (C.c_int64 * len(sets))(*[s[0].shape[0] for s in sets])
-    nws = int(_lib.nmf_brdf_mlp_bwd_segments_workspace_bytes(Rs, C.c_int32(len(sets)), C.c_int32(max_workgroups)))
-    ws = torch.empty(max(nws, 4) // 4, dtype=torch.float32, device=dev)
-    wp = [None] * 6 if image is not None else [_p(w, torch.float32) for w in weights]
-    _check(_lib.nmf_brdf_mlp_bwd_segments(_p(image) if image is not None else None, *wp, arr, C.c_int32(len(sets)),
-                                          *[_p(g) for g in grads], C.c_int32(max_workgroups), _p(ws), C.c_int64(nws), _stream()),
-           "nmf_brdf_mlp_bwd_segments")
-    return outs
+    return HOST_EXT.brdf_mlp_bwd_sets(list(weights or ()), list(sets), list(grads), int(max_workgroups), _stream(), image)
 
 
 def heads_fwd(feat, W, b, hp):
@@ -786,42 +640,15 @@ def bounce_index(counts, xyzt=None):
 
 def bounce_prep_fwd_heads(bidx, normals, app, head_W, head_b, hp, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough, row_inputs=1):
     """heads_fwd(app, head_W, head_b, hp) + bounce_prep_fwd(..., heads, ...) in one launch -> (heads, V, N, r1, f0, diffuse, feat, xyz)"""
-    Mb = bidx.shape[0]
-    dev = normals.device
-    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
-    heads, V, N, r1, f0, diff, feat, xyz = f(Mb, 11), f(Mb, 3), f(Mb, 3), f(Mb), f(Mb, 3), f(Mb, 3), f(Mb, 24), f(Mb, 3)
-    if Mb:
-        _check(_lib.nmf_bounce_prep_fwd_heads(_p(bidx, torch.int32), C.c_int64(Mb), _p(normals, torch.float32), _p(app, torch.float32),
-                                              _p(head_W, torch.float32), _p(head_b, torch.float32), *[C.c_float(v) for v in hp],
-                                              _p(xyzt, torch.float32), _p(ray_id, torch.int32), _p(rays, torch.float32),
-                                              _p(conv, torch.float32), _p(feat_noise, torch.float32), C.c_float(anoise),
-                                              C.c_float(min_rough), C.c_int32(int(row_inputs)), _p(heads), _p(V), _p(N), _p(r1), _p(f0),
-                                              _p(diff), _p(feat), _p(xyz), _stream()), "nmf_bounce_prep_fwd_heads")
-    return heads, V, N, r1, f0, diff, feat, xyz
+    return HOST_EXT.bounce_prep_fwd_heads(bidx, normals, app, head_W, head_b, list(hp), xyzt, ray_id, rays, conv, feat_noise, anoise,
+                                          min_rough, int(row_inputs), _stream())
 
 
 def bounce_index_select(weights, u, mode, mul, add=0.0, sum_w=1.0, xyzt=None):
     """select_bounces(weights, u, mode, mul, add, sum_w) + bounce_index(counts, xyzt) without materialising the counts: the count of a
     sample is evaluated inside the two launches of the index (nmf_bounce_index_select).  sum_w: float or 0-d device tensor."""
-    M = weights.shape[0]
-    dev = weights.device
-    rows = torch.empty((max(M, 1), 4), dtype=torch.float32, device=dev) if xyzt is not None else None
-    bidx = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    row_off = torch.empty(M + 1, dtype=torch.int64, device=dev)
-    inv = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    cnt_rows = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
-    totals = torch.empty(2, dtype=torch.int64, device=dev)
-    nbytes = _lib.nmf_bounce_index_workspace_bytes(C.c_int64(M))
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
     dev_sum = sum_w if isinstance(sum_w, torch.Tensor) else None
-    _check(_lib.nmf_bounce_index_select(_p(weights, torch.float32) if M else None, _p(u, torch.float32) if M else None, C.c_int32(mode),
-                                        C.c_float(mul), C.c_float(add), C.c_float(1.0 if dev_sum is not None else sum_w),
-                                        _p(dev_sum, torch.float32), C.c_int64(M), None, _p(bidx), _p(row_off), _p(cnt_rows), _p(inv),
-                                        _p(totals), _p(xyzt, torch.float32) if (xyzt is not None and M) else None, _p(rows), _p(ws),
-                                        C.c_int64(nbytes), None, C.c_int64(0), _stream()), "nmf_bounce_index_select")
-    if xyzt is not None:
-        return bidx, row_off, cnt_rows, inv[:M], totals, rows
-    return bidx, row_off, cnt_rows, inv[:M], totals
+    return HOST_EXT.bounce_index_select(weights, u, mode, mul, add, 1.0 if dev_sum is not None else sum_w, dev_sum, xyzt, _stream())
 
 
 def bounce_prep_fwd(bidx, normals, app, heads, xyzt, ray_id, rays, conv, feat_noise, anoise, min_rough, row_inputs=False):
@@ -871,17 +698,12 @@ def l1_mean_fwd(tensors):
 
 def l1_mean_bwd(tensors, d_out, out=None):
     """-> gradients in the tensors' own memory order; out = existing gradient tensors of the same storage order to ADD into"""
-    if out is not None:
-        HOST_EXT.l1_mean_bwd_into(list(tensors), d_out, list(out), _stream())
-        return out
-    n = len(tensors)
-    grads = [torch.empty_like(t, memory_format=torch.preserve_format) for t in tensors]
-    ptrs = (C.c_void_p * n)(*[_dense_f32(t) for t in tensors])
-    gptrs = (C.c_void_p * n)(*[_dense_f32(g) for g in grads])
-    numel = (C.c_int64 * n)(*[t.numel() for t in tensors])
-    _check(_lib.nmf_l1_mean_bwd(ptrs, numel, C.c_int32(n), _p(d_out, torch.float32), gptrs, C.c_int32(0), _stream()),
-           "nmf_l1_mean_bwd")
-    return grads
+    if out is None:
+        grads = [torch.empty_like(t, memory_format=torch.preserve_format) for t in tensors]
+        HOST_EXT.l1_mean_bwd_into(list(tensors), d_out, grads, False, _stream())
+        return grads
+    HOST_EXT.l1_mean_bwd_into(list(tensors), d_out, list(out), True, _stream())
+    return out
 
 
 def loss_mix_fwd(tensors, weights, scale):
@@ -918,24 +740,12 @@ def loss_head(pred, gt, d_out, scale, w_pred, w_a, w_b):
     """sqerr_fwd + loss_mix_bwd + sqerr_bwd of one chunk in one launch -> (loss 0-d, d_pred [B,3], g_a [B], g_b [B]):
     loss = sum (clip(pred) - clip(gt))^2 (summed in a fixed order, written: no zero fill), d_pred = 2 (pred - clip(gt)) *
     (d_out scale w_pred) inside [0,1], g_a / g_b filled with d_out scale w_a / w_b."""
-    B = pred.shape[0]
-    loss = torch.empty((), dtype=torch.float32, device=pred.device)
-    d_pred = torch.empty_like(pred)
-    g_a = torch.empty(B, dtype=torch.float32, device=pred.device)
-    g_b = torch.empty(B, dtype=torch.float32, device=pred.device)
-    ws = loss_head_workspace(pred.device, B)
-    _check(_lib.nmf_loss_head(_p(pred, torch.float32), _p(gt, torch.float32), C.c_int64(B), _p(d_out, torch.float32),
-                              C.c_float(scale), C.c_float(w_pred), C.c_float(w_a), C.c_float(w_b), _p(loss), _p(d_pred),
-                              _p(g_a), _p(g_b), C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel()), _stream()), "nmf_loss_head")
-    return loss, d_pred, g_a, g_b
+    return HOST_EXT.loss_head(pred, gt, d_out, scale, w_pred, w_a, w_b, loss_head_workspace(pred.device, pred.shape[0]), _stream())
 
 
 def bg_adjoint(acc, d_rgb):
     """(1 - acc)[:, None] * d_rgb in one launch (the background adjoint nmf_ray_compose_bwd leaves to the caller)"""
-    d_bg = torch.empty_like(d_rgb)
-    _check(_lib.nmf_bg_adjoint(_p(acc, torch.float32), _p(d_rgb.contiguous(), torch.float32), C.c_int64(acc.shape[0]), _p(d_bg),
-                               _stream()), "nmf_bg_adjoint")
-    return d_bg
+    return HOST_EXT.bg_adjoint(acc, d_rgb, _stream())
 
 
 def sqerr_fwd(pred, gt):
@@ -1129,20 +939,11 @@ def material_maps(app, normals, weight, offsets, rays, head_W, head_b, head_p, c
     diffuse | tint | spec, 3 columns each).  app [M,24], normals [M,3], weight [M], offsets int64 [B+1], rays [B,6], head_W [11,24],
     head_b [11], head_p = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias), conv [9,3], acc [B], bg [3]; the bounce rows
     inv int32 [M], row_off int64 [Mb+1], cnt int32 [Mb], incoming / brdf_weight [R,3] (all None: no row, spec and tint are 0)."""
-    B, M = offsets.shape[0] - 1, app.shape[0]
-    Mb = 0 if row_off is None else row_off.shape[0] - 1
-    R = 0 if incoming is None else incoming.shape[0]
+    _p(app, torch.float32)          # refuses host tensors before the stream is asked for (there is none without a GPU)
     if len(head_p) != 5:
         raise NmfHipError("material_maps: head_p = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)")
-    out = torch.empty((B, 15), dtype=torch.float32, device=offsets.device)
-    hp = [C.c_float(float(v)) for v in head_p]
-    _check(_lib.nmf_material_maps(_p(app, torch.float32), _p(normals, torch.float32), _p(weight, torch.float32),
-                                  _p(offsets, torch.int64), C.c_int64(B), C.c_int64(M), _p(rays, torch.float32),
-                                  _p(head_W, torch.float32), _p(head_b, torch.float32), *hp, _p(conv, torch.float32),
-                                  _p(inv, torch.int32), _p(row_off, torch.int64), _p(cnt, torch.int32), C.c_int64(Mb),
-                                  _p(incoming, torch.float32), _p(brdf_weight, torch.float32), C.c_int64(R),
-                                  _p(acc, torch.float32), _p(bg, torch.float32), _p(out), _stream()), "nmf_material_maps")
-    return out
+    return HOST_EXT.material_maps(app, normals, weight, offsets, rays, head_W, head_b, [float(v) for v in head_p], conv, inv, row_off, cnt,
+                                  incoming, brdf_weight, acc, bg, _stream())
 
 
 # ---- mesh export: marching cubes over a dense volume (csrc/mesh.hip) ------------------------------------------------------

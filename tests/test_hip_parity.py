@@ -436,8 +436,8 @@ def test_env_lookup_golden_and_gradients():
                                            [sd["bg_module.bg_mat"], sd["bg_module.mipbias"], d_or])
     d_sat = torch.zeros(sat.shape[-2:] + (4,), device=sat.device)        # channel-interleaved adjoint table
     d_pole = torch.zeros(2, 3, device=DEV)
-    d_dirs, d_mip = hip.sat_lookup_bwd(sat, dirs.to(DEV).contiguous(), sa.to(DEV).contiguous(), 1.0, c.to(DEV), d_sat, d_pole,
-                                       want_mipbias=True)
+    d_mip = torch.zeros(1, device=DEV)
+    d_dirs = hip.sat_lookup_bwd(sat, dirs.to(DEV).contiguous(), sa.to(DEV).contiguous(), 1.0, c.to(DEV), d_sat, d_pole, d_mip=d_mip)
     d_bg = hip.sat_build_bwd(d_sat, bg.to(DEV), act, d_pole)
     assert_close(d_bg.cpu()[None], gb_o, rtol=2e-3, atol=2e-4 * float(gb_o.abs().max()), what="grad bg_mat")
     assert_close(d_dirs.cpu(), gd_o, rtol=5e-3, atol=5e-4 * float(gd_o.abs().max()), what="grad dirs")
@@ -1817,6 +1817,151 @@ def test_host_extension_wrappers_vs_cpu_references():
         hip.composite_fwd(sig.cpu(), dist, off, Mb, 25.0)
     with pytest.raises(hip.NmfHipError):
         hip.segment_sum(vals, None, off, Mb, lanes=3)
+    # ... also from the wrappers whose single implementation the fused step shares: a host tensor in front is refused (no launch)
+    z = lambda *s: torch.zeros(*s, device=DEV)  # noqa: E731
+    zi = lambda *s: torch.zeros(*s, dtype=torch.int32, device=DEV)  # noqa: E731
+    hp = (1.0, 0.0, 0.0, 0.0, 0.0)
+    with pytest.raises(hip.NmfHipError):
+        hip.bounce_prep_fwd_heads(torch.zeros(4, dtype=torch.int32), z(4, 3), z(4, 24), z(11, 24), z(11), hp, z(4, 4), zi(4), z(1, 6),
+                                  z(9, 3), None, 0.0, 0.02, 2)
+    with pytest.raises(hip.NmfHipError):
+        hip.bounce_index_select(w.cpu(), u_c.to(DEV), 0, 64.0)
+    with pytest.raises(hip.NmfHipError):
+        hip.material_maps(torch.zeros(4, 24), z(4, 3), z(4), torch.tensor([0, 4], device=DEV), z(1, 6), z(11, 24), z(11), hp, z(9, 3),
+                          z(1), z(3))
+    with pytest.raises(hip.NmfHipError):
+        hip.loss_head(torch.zeros(4, 3), z(4, 3), torch.ones((), device=DEV), 1.0, 1.0, 0.5, 0.5)
+    with pytest.raises(hip.NmfHipError):
+        hip.bg_adjoint(torch.zeros(4), z(4, 3))
+    mlp_w = [z(64, 66), z(64), z(64, 64), z(64), z(4, 64), z(4)]
+    mlp_set = (z(2, 3), z(2, 3), z(2, 24), z(2), zi(2), z(2, 3), zi(2, 4), z(2, 3))
+    with pytest.raises(hip.NmfHipError):
+        hip.brdf_mlp_bwd_segments([mlp_w[0].cpu()] + mlp_w[1:], [mlp_set], [torch.zeros_like(t) for t in mlp_w])
+    with pytest.raises(hip.NmfHipError):
+        hip.vm_bin_plan(tabs[0], [xyz_c])
+
+
+def _same_bits(a, b):
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.gpu
+def test_vm_unpack_density_grad_argument_forms_give_the_same_bits():
+    """out= / l1= of vm_unpack_density_grad (the form the fused step calls) against the allocating forms: one implementation, the same
+    kernel on the same inputs, so the same bits; out= hands back the tensors it was given; a parameter of another size is refused"""
+    hip = _hip()
+    G = 32
+    cfg = O.Cfg(grid=G)
+    d = cfg.derived()
+    p = hip.vm_params(d["aabb"], d["inv"], cfg.density_shift, G)
+    gen = torch.Generator().manual_seed(G)
+    g_dpk = [torch.randn(G, G, 48, generator=gen).to(DEV) for _ in range(3)]
+    g_dlk = [torch.randn(G, 32, generator=gen).to(DEV) for _ in range(3)]
+    cl = lambda t: t.to(DEV).contiguous(memory_format=torch.channels_last)  # noqa: E731
+    xs = [cl(torch.randn(1, 16, G, G, generator=gen)) for _ in range(3)] + [cl(torch.randn(1, 16, G, 1, generator=gen)) for _ in range(3)]
+    xs[0][0, :, ::3, ::5] = 0.0
+    scale = torch.full((), 3e-4, dtype=torch.float32, device=DEV)
+    held = lambda: ([cl(torch.full((1, 16, G, G), math.nan)) for _ in range(3)],  # noqa: E731
+                    [cl(torch.full((1, 16, G, 1), math.nan)) for _ in range(3)])
+    plain = hip.vm_unpack_density_grad(p, g_dpk, g_dlk)
+    with_l1 = hip.vm_unpack_density_grad(p, g_dpk, g_dlk, l1=(xs, scale))
+    assert not torch.equal(plain[0][0], with_l1[0][0])
+    for l1, ref in ((None, plain), ((xs, scale), with_l1)):
+        gp, gl = held()
+        r = hip.vm_unpack_density_grad(p, g_dpk, g_dlk, out=(gp, gl), l1=l1)
+        assert all(a is b for a, b in zip(list(r[0]) + list(r[1]), gp + gl))
+        assert _same_bits(gp, list(ref[0])) and _same_bits(gl, list(ref[1]))
+    bad = xs[:5] + [cl(torch.randn(1, 16, G + 1, 1, generator=gen))]
+    with pytest.raises(hip.NmfHipError):
+        hip.vm_unpack_density_grad(p, g_dpk, g_dlk, l1=(bad, scale))
+    with pytest.raises(hip.NmfHipError):
+        hip.vm_unpack_density_grad(p, g_dpk, g_dlk, out=held(), l1=(bad, scale))
+
+
+@pytest.mark.gpu
+def test_env_table_wrappers_argument_forms_give_the_same_bits():
+    """sat_build / sat_build_bwd / sh_project: the allocating form and out=, a contiguous and a non-contiguous [1,3,H,W] bg_mat -- one
+    implementation each, so the same bits"""
+    hip = _hip()
+    H, W = 16, 32
+    gen = torch.Generator().manual_seed(H)
+    wide = (-0.6 + 0.7 * torch.randn(1, 3, H, 2 * W, generator=gen)).to(DEV)
+    view = wide[..., :W]
+    assert not view.is_contiguous() and view.shape == (1, 3, H, W)
+    ref = hip.sat_build(view.contiguous(), pole=True, interleaved=True)
+    assert [tuple(t.shape) for t in ref] == [(3, H, W), (3, H, W), (2, 3), (H, W, 4)]
+    assert _same_bits(hip.sat_build(view, pole=True, interleaved=True), ref)
+    held = hip.sat_build(wide[..., W:].contiguous(), pole=True, interleaved=True)
+    assert not torch.equal(held[1], ref[1])
+    again = hip.sat_build(view, out=held, pole=True, interleaved=True)
+    assert all(a is b for a, b in zip(again, held)) and _same_bits(again, ref)
+    # the table backward consumes d_sat in place: a clone per call
+    d_sat = torch.randn(H, W, 4, generator=gen).to(DEV)
+    d_pole = torch.randn(2, 3, generator=gen).to(DEV)
+    act = ref[0]
+    d_ref = hip.sat_build_bwd(d_sat.clone(), view.contiguous(), act, d_pole)
+    assert d_ref.shape == (3, H, W) and float(d_ref.abs().max()) > 0
+    o = torch.full_like(d_ref, math.nan)
+    assert hip.sat_build_bwd(d_sat.clone(), view.contiguous(), act, d_pole, out=o) is o and torch.equal(o, d_ref)
+    assert torch.equal(hip.sat_build_bwd(d_sat.clone(), view, act, d_pole), d_ref)
+    o = torch.full_like(d_ref, math.nan)
+    assert hip.sat_build_bwd(d_sat.clone(), view, act, d_pole, out=o) is o and torch.equal(o, d_ref)
+    n, K = 64, 9
+    vals, wq, shA = torch.randn(n, 3, generator=gen).to(DEV), torch.randn(n, K, generator=gen).to(DEV), torch.rand(K, generator=gen).to(DEV)
+    fresh = hip.sh_project(vals, wq, shA)
+    o = (torch.full((K, 3), math.nan, device=DEV), torch.full((K, 3), math.nan, device=DEV))
+    got = hip.sh_project(vals, wq, shA, out=o)
+    assert got[0] is o[0] and got[1] is o[1] and _same_bits(got, fresh) and fresh[0].shape == (K, 3)
+
+
+@pytest.mark.gpu
+def test_l1_mean_bwd_argument_forms_give_the_same_bits():
+    """the allocating form (gradients written) against out= (gradients added, here to zeros) and against d_out * sign(x) / numel:
+    the kernel's g = +-(d_out / n), one IEEE division, is that expression bit for bit.  The expression is evaluated on host copies:
+    there torch divides by the scalar, on the device it multiplies by the scalar's rounded reciprocal, which is another number
+    for n = 112 (3 / 112 != 3 * (1 / 112) in fp32)"""
+    hip = _hip()
+    gen = torch.Generator().manual_seed(5)
+    ts = [torch.randn(1, 16, 5, 5, generator=gen).to(DEV).contiguous(memory_format=torch.channels_last),
+          torch.randn(1, 16, 7, 1, generator=gen).to(DEV).contiguous(memory_format=torch.channels_last),
+          torch.randn(300, generator=gen).to(DEV)]
+    ts[0][0, 3, 1, 2] = 0.0
+    ts[2][::7] = 0.0
+    d_out = torch.full((), 3.0, dtype=torch.float32, device=DEV)
+    fresh = hip.l1_mean_bwd(ts, d_out)
+    zeros = [torch.zeros_like(t, memory_format=torch.preserve_format) for t in ts]
+    added = hip.l1_mean_bwd(ts, d_out, out=zeros)
+    assert all(a is b for a, b in zip(added, zeros))
+    for t, f, a in zip(ts, fresh, added):
+        assert f.stride() == t.stride()
+        ref = d_out.cpu() * torch.sign(t.cpu()) / t.numel()
+        assert torch.equal(f, a) and torch.equal(f.cpu(), ref)
+
+
+@pytest.mark.gpu
+def test_material_maps_without_bounce_rows():
+    """hip.material_maps with inv = row_off = cnt = incoming = brdf_weight = None (what no other test passes): tint and spec stay zero
+    under a black background, and the sample-only maps are those of a call with empty row tensors (Mb = 0)"""
+    hip = _hip()
+    B, M = 4, 16
+    gen = torch.Generator().manual_seed(4)
+    r = lambda *s: torch.randn(*s, generator=gen).to(DEV)  # noqa: E731
+    app, normals = r(M, 24), torch.nn.functional.normalize(r(M, 3), dim=-1)
+    weight = (torch.rand(M, generator=gen) * 0.2).to(DEV)
+    offsets = torch.tensor([0, 5, 5, 9, 16], dtype=torch.int64, device=DEV)
+    rays = torch.cat([r(B, 3), torch.nn.functional.normalize(r(B, 3), dim=-1)], 1).contiguous()
+    head_W, head_b, conv = r(11, 24) * 0.3, r(11) * 0.1, r(9, 3)
+    acc = torch.rand(B, generator=gen).to(DEV)
+    bg = torch.zeros(3, device=DEV)
+    hp = (1.3, -0.4, 0.1, -0.2, -0.7)
+    none = hip.material_maps(app, normals, weight, offsets, rays, head_W, head_b, hp, conv, acc, bg)
+    assert none.shape == (B, 15) and none.dtype == torch.float32
+    assert int(none[:, 9:15].count_nonzero()) == 0 and float(none[:, 0:9].abs().max()) > 0
+    empty = hip.material_maps(app, normals, weight, offsets, rays, head_W, head_b, hp, conv, acc, bg,
+                              inv=torch.full((M,), -1, dtype=torch.int32, device=DEV), row_off=torch.zeros(1, dtype=torch.int64, device=DEV),
+                              cnt=torch.zeros(0, dtype=torch.int32, device=DEV), incoming=torch.zeros(0, 3, device=DEV),
+                              brdf_weight=torch.zeros(0, 3, device=DEV))
+    assert torch.equal(none[:, 0:9], empty[:, 0:9]) and torch.equal(none, empty)
 
 
 @pytest.mark.gpu

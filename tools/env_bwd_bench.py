@@ -34,9 +34,9 @@ def main():
     calls = []
     orig = hip.sat_lookup_bwd
 
-    def spy(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, want_dirs=True, want_mipbias=None, sc=None):
+    def spy(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, want_dirs=True, sc=None):
         calls.append((sat, dirs.clone(), sa.clone(), mipbias, d_out.clone(), sc))
-        return orig(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, want_mipbias, sc)
+        return orig(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, sc)
 
     hip.sat_lookup_bwd = spy
     tr.step(*batches[2], focal, noise=noise, update_controllers=False, fixed_chunk=bench.CHUNK)
