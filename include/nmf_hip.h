@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 120
+#define NMF_ABI_VERSION 121
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -787,6 +787,24 @@ int64_t nmf_tv_workspace_bytes(const int32_t* shape, const int32_t* kind, int32_
 int nmf_tv_fwd_bwd(const float* const x[], float* const g[], const int32_t* shape, const int64_t* x_stride, const int64_t* g_stride,
                    const int32_t* kind, const float w[], int32_t count, const float* scale_dev, float* value_out, void* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Relighting: a spherical radiance function resampled into an IntegralEquirect texel grid under a rotation (no reference
+ * counterpart as a function: scripts/car_rotating_lights.ipynb rotates lights in a notebook, scripts/pano2cube.py imports a
+ * panorama by fitting).  dst [3][H][W] (a bg_mat) = log(max(gain * mean of supersample^2 stratified sub-samples of the texel's
+ * extent, 1e-8)); a NaN becomes the floor.  Texel (i, j) covers ix in (j - 1, j], iy in (i - 1, i] of the summed-area table's
+ * coordinates, each sub-sample becomes a direction d, and the source is read along R^T d (row-major R = r00..r22:
+ * the lighting rotated by R), bilinearly, in LINEAR radiance:
+ *   kind 0  src [3][Hs][Ws], the activated table of a module map (nmf_sat_build's `activated`): texel centres at ix = j - 1/2,
+ *           columns periodic over 1..Ws-1, rows clamped to 1..Hs-1
+ *   kind 1  src [Hs][Ws][3], a panorama in pano2env.pixel_directions' parameterisation (scripts/pano2cube.py:101-109): columns
+ *           periodic with period Ws - 1, rows clamped
+ * One thread per destination texel, no atomics: the same bytes on every run.  Refused (nothing launched): a null pointer or a size
+ * below 4, an unknown kind, a gain that is not finite and positive, max|R^T R - I| > 1e-4 (NMF_EINVAL); supersample outside 1..8
+ * (NMF_ERANGE). */
+int nmf_env_resample(const float* src, int32_t kind, int32_t Hs, int32_t Ws, float r00, float r01, float r02, float r10, float r11,
+                     float r12, float r20, float r21, float r22, float gain, int32_t supersample, float* dst, int32_t H, int32_t W,
+                     void* stream);
 
 #ifdef __cplusplus
 }

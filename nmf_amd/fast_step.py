@@ -180,6 +180,13 @@ class TrainPass:
         for cx in self._ctxs:
             setattr(cx.core, name, value)
 
+    def invalidate_tables(self):
+        """a module the derived tables are built from was REPLACED (relight.relit swaps nerf.bg_module): _param_token's cached
+        parameter list still names the replaced module's parameters, so forget it and rebuild the tables before the next chunk"""
+        self._token_params = None
+        self._token_plist = None
+        self._tables_token = None
+
     def _param_token(self):
         """(version, storage) of every parameter the derived tables are built from: equal token = equal tables"""
         ps = self._token_params

@@ -97,6 +97,7 @@ EXPORTS = [
     "nmf_material_maps",
     "nmf_mc_count", "nmf_mc_emit", "nmf_mc_workspace_bytes", "nmf_mc_case_triangles",
     "nmf_tv_fwd_bwd", "nmf_tv_workspace_bytes",
+    "nmf_env_resample",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -501,6 +502,45 @@ def sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip=None, wan
     dirs (None without want_dirs)."""
     return HOST_EXT.sat_lookup_bwd(sat, dirs, sa, mipbias, d_out, d_sat, d_pole, d_mip, want_dirs, sc,
                                    int(ENV_BINNED_MIN_LOOKUPS), _stream())
+
+
+ENV_SRC_MODULE, ENV_SRC_PANORAMA = 0, 1
+
+
+def env_resample(src, kind, R, gain, supersample, out):
+    """Resample a spherical radiance function into a bg_mat under the rotation R (nmf_env_resample; nmf_amd/relight.py).
+    src: float32 LINEAR radiance, [3,Hs,Ws] planar (kind ENV_SRC_MODULE: the activated table of a module) or [Hp,Wp,3] interleaved
+    (kind ENV_SRC_PANORAMA); R: 3x3 rotation (host numbers); out: float32 [3,H,W] or [1,3,H,W], written in place with
+    log(max(gain * mean, 1e-8)).  Returns out."""
+    for name, t in (("src", src), ("out", out)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise NmfHipError(f"env_resample: {name} must be a device tensor (no CPU path)")
+        if t.dtype != torch.float32:
+            raise NmfHipError(f"env_resample: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise NmfHipError(f"env_resample: {name} must be contiguous")
+    if src.device != out.device:
+        raise NmfHipError("env_resample: src and out are on different devices")
+    if kind == ENV_SRC_MODULE:
+        if src.dim() != 3 or src.shape[0] != 3:
+            raise NmfHipError(f"env_resample: a module source is [3,Hs,Ws], got {tuple(src.shape)}")
+        Hs, Ws = src.shape[1], src.shape[2]
+    elif kind == ENV_SRC_PANORAMA:
+        if src.dim() != 3 or src.shape[2] != 3:
+            raise NmfHipError(f"env_resample: a panorama source is [Hp,Wp,3], got {tuple(src.shape)}")
+        Hs, Ws = src.shape[0], src.shape[1]
+    else:
+        raise NmfHipError(f"env_resample: unknown source kind {kind}")
+    if out.dim() not in (3, 4) or out.shape[-3] != 3 or out.numel() != 3 * out.shape[-2] * out.shape[-1]:
+        raise NmfHipError(f"env_resample: out is [3,H,W] or [1,3,H,W], got {tuple(out.shape)}")
+    if src.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+        raise NmfHipError("env_resample: src and out share their storage")
+    r = [float(v) for v in np.asarray(R, dtype=np.float64).reshape(-1)]
+    if len(r) != 9:
+        raise NmfHipError("env_resample: R must be 3x3")
+    _check(_lib.nmf_env_resample(_p(src), int(kind), Hs, Ws, *r, float(gain), int(supersample), _p(out), out.shape[-2], out.shape[-1],
+                                 _stream()), "nmf_env_resample")
+    return out
 
 
 # ---- shading helpers -------------------------------------------------------------------------------

@@ -10,7 +10,12 @@ panorama pixels looked up along their directions at a sharp footprint (log-solid
 written with torch.save and the fitted map as `<prefix>pano.exr` next to it.  The panorama is read by nmf_amd.exr (the
 image has no imageio / OpenEXR; NONE / RLE / ZIP(S) / DWAA / DWAB compressed files, i.e. the reference's backgrounds/*.exr as
 they are).  `render.py --fixed-bg` loads the result at ITS OWN
-resolution (the reference hard-codes 512 there while this tool's default is 1024)."""
+resolution (the reference hard-codes 512 there while this tool's default is 1024).
+
+    python -m nmf_amd.pano2env backgrounds/forest.exr --output log/forest.th --direct
+
+--direct writes the same two files from relight.import_panorama instead of the fit: the panorama's radiance, area-averaged per
+texel, in closed form (one kernel launch)."""
 import argparse
 import json
 import math
@@ -68,6 +73,33 @@ def fit(pano, res=1024, epochs=1000, batch_size=4096 * 50, device="cuda", seed=0
     return bg, psnr
 
 
+def read_panorama(path):
+    """.exr (nmf_amd.exr), .npy or an 8-bit image -> float [H,W,3]"""
+    low = str(path).lower()
+    if low.endswith(".exr"):
+        return exr.imread(path)[..., :3]
+    if low.endswith(".npy"):
+        return np.load(path)[..., :3]
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.float32) / 255.0
+
+
+@torch.no_grad()
+def panorama_error(bg, pano, batch_size=4096 * 50, seed=0):
+    """the figure fit() logs (the script's -10 log10 of the mean clipped photometric error at the sharpest footprint), over
+    batch_size random pixels of the panorama"""
+    dev = bg.get_device()
+    colors = torch.as_tensor(np.ascontiguousarray(pano), dtype=torch.float32, device=dev)
+    H, W, _ = colors.shape
+    colors = colors.reshape(-1, 3)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    inds = torch.randperm(H * W, device=dev, generator=g)[:min(batch_size, H * W)]
+    rows, cols = torch.div(inds, W, rounding_mode="floor").float(), (inds % W).float()
+    out = bg(pixel_directions(rows, cols, H, W), torch.full((inds.shape[0],), math.log(1e-5), device=dev))
+    photo = torch.sqrt((out.clip(0, 1) - colors[inds].clip(0, 1)) ** 2 + 1e-8).mean()
+    return -10.0 * math.log10(float(photo))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("input")
@@ -75,21 +107,24 @@ def main(argv=None):
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--epochs", type=int, default=1000)
     ap.add_argument("--batch", type=int, default=4096 * 50)
+    ap.add_argument("--direct", action="store_true",
+                    help="import the panorama in closed form (relight.import_panorama) instead of fitting the map to it")
     args = ap.parse_args(argv)
-    if args.input.lower().endswith(".exr"):
-        pano = exr.imread(args.input)[..., :3]
-    elif args.input.lower().endswith(".npy"):
-        pano = np.load(args.input)[..., :3]
-    else:
-        from PIL import Image
-        pano = np.asarray(Image.open(args.input).convert("RGB"), dtype=np.float32) / 255.0
+    pano = read_panorama(args.input)
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    bg, psnr = fit(pano, args.res, args.epochs, args.batch, dev, log=lambda r: print(json.dumps(r), flush=True))
+    if args.direct:
+        from .relight import import_panorama
+        bg = import_panorama(pano, args.res, device=dev)
+        psnr = panorama_error(bg, pano, args.batch)
+    else:
+        bg, psnr = fit(pano, args.res, args.epochs, args.batch, dev, log=lambda r: print(json.dumps(r), flush=True))
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     torch.save(bg.state_dict(), args.output)
     stem = os.path.splitext(os.path.basename(args.output))[0]
     bg.save(os.path.dirname(os.path.abspath(args.output)), prefix=stem + "_")
     rec = dict(output=args.output, resolution=args.res, panorama=list(pano.shape), psnr=psnr)
+    if args.direct:
+        rec["direct"] = True
     print(json.dumps(rec), flush=True)
     return rec
 

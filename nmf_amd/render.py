@@ -14,6 +14,14 @@ Prints one JSON line: frames, rays/s (render to completion, eval_batch_size rays
 frames, mean.txt and stats.yaml go to DIR, and the line gains ssim, norm_err and the evaluation's render / metric seconds.
 --material-maps adds the material maps of every view (renderer.py:433-463): albedo/, roughness/, tint/, diffuse/ PNGs, spec/ and
 rgbd/ (depth) EXRs.
+
+    python -m nmf_amd.render --ckpt log/s1.th --env-rotate 90 0 0                      (the scene's own lighting, turned)
+    python -m nmf_amd.render --ckpt log/s1.th --fixed-bg studio.exr --bg-res 512 --light-turntable 36 --out imgs/
+
+Relighting (nmf_amd/relight.py): --fixed-bg also takes a panorama (.exr, .npy or an image), imported directly at
+--bg-res without an optimisation run; --env-rotate YAW PITCH ROLL (degrees, +z up) rotates the lighting -- the checkpoint's own map or
+the --fixed-bg one; --light-turntable N then renders view 0 N times under a further yaw of 360 k / N (light_000.png ... in --out) and
+the line gains light_frames and, per frame, the seconds of the environment update and of the render.
 """
 import argparse
 import json
@@ -29,8 +37,16 @@ from .noise import DeviceNoise
 from .renderer import psnr_8bit, render_images
 
 
-def load_fixed_bg(path, device):
-    """train.py:96-138: an IntegralEquirect with mipbias 0 / activation exp, its learning rates zeroed"""
+PANORAMA_SUFFIXES = (".exr", ".npy", ".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+
+
+def load_fixed_bg(path, device, bg_res=512):
+    """train.py:96-138: an IntegralEquirect with mipbias 0 / activation exp, its learning rates zeroed.  A panorama (.exr, .npy, an
+    image) instead of a state_dict is imported directly at bg_res (relight.import_panorama)"""
+    if str(path).lower().endswith(PANORAMA_SUFFIXES):
+        from .pano2env import read_panorama
+        from .relight import import_panorama
+        return import_panorama(read_panorama(path), bg_res, device=device)
     from .checkpoint import load_checkpoint
     sd = load_checkpoint(path)
     sd = sd.get("state_dict", sd) if isinstance(sd, dict) and "bg_mat" not in sd else sd
@@ -53,6 +69,33 @@ def render_frames(nerf, rays, focal, chunk, noise):
     return torch.stack(out), time.perf_counter() - t0
 
 
+@torch.no_grad()
+def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None):
+    """view rays [1, h*w, 6] rendered n times under nerf's lighting turned by a yaw of 360 k / n: ONE map module is rewritten per frame
+    (relight.rotate_env(out=)), its tables rebuild in place.  -> the keys the JSON line gains; light_%03d.png in out_dir"""
+    from . import relight
+    base = nerf.bg_module
+    turned = relight.rotate_env(base, relight.rotation(0.0))
+    env_s, render_s = [], []
+    with relight.relit(nerf, turned):
+        for k in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            relight.rotate_env(base, relight.rotation(yaw=360.0 * k / n), out=turned)
+            turned._tables_checked()                                         # SAT rebuild
+            turned.get_spherical_harmonics(100)                             # SH irradiance of the turned map
+            torch.cuda.synchronize()
+            env_s.append(round(time.perf_counter() - t0, 6))
+            rgb, dt = render_frames(nerf, rays, focal, chunk, noise)
+            render_s.append(round(dt, 6))
+            if out_dir:
+                from PIL import Image
+                os.makedirs(out_dir, exist_ok=True)
+                a = (rgb[0].clip(0, 1).reshape(wh[1], wh[0], 3) * 255).byte().cpu().numpy()
+                Image.fromarray(a).save(os.path.join(out_dir, f"light_{k:03d}.png"))
+    return dict(light_frames=n, light_env_seconds=env_s, light_render_seconds=render_s)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", required=True)
@@ -68,7 +111,14 @@ def main(argv=None):
                     help="with --datadir: evaluate the test views (PSNR, SSIM, normal error) into this directory")
     ap.add_argument("--material-maps", action="store_true",
                     help="with --eval-dir: also write the material maps (albedo/, roughness/, tint/, diffuse/ PNGs, spec/ and rgbd/ EXRs)")
+    ap.add_argument("--bg-res", type=int, default=512, help="resolution a --fixed-bg PANORAMA is imported at")
+    ap.add_argument("--env-rotate", type=float, nargs=3, default=None, metavar=("YAW", "PITCH", "ROLL"),
+                    help="rotate the lighting (degrees, +z up): the checkpoint's own environment map or the --fixed-bg one")
+    ap.add_argument("--light-turntable", type=int, default=0, metavar="N",
+                    help="render view 0 N times under a yaw of 360 k / N of the lighting (light_000.png ... in --out)")
     args = ap.parse_args(argv)
+    if args.light_turntable < 0:
+        ap.error("--light-turntable takes a number of frames")
     if args.eval_dir and not args.datadir:
         ap.error("--eval-dir needs --datadir (ground truth of a Blender scene)")
     if args.material_maps and not args.eval_dir:
@@ -87,7 +137,10 @@ def main(argv=None):
         rays, near_far, wh = r.reshape(args.views, -1, 6).to(dev), tuple(args.near_far), [args.res, args.res]
     nerf = TensorNeRF.load(args.ckpt, near_far=list(near_far), device=dev)
     if args.fixed_bg:
-        nerf.bg_module = load_fixed_bg(args.fixed_bg, dev)
+        nerf.bg_module = load_fixed_bg(args.fixed_bg, dev, args.bg_res)
+    if args.env_rotate is not None:
+        from . import relight
+        nerf.bg_module = relight.rotate_env(nerf.bg_module, relight.rotation(*args.env_rotate))
     nerf.eval()
     chunk = args.chunk or nerf.eval_batch_size
     noise = DeviceNoise(dev, seed=11)
@@ -103,6 +156,8 @@ def main(argv=None):
         for i in range(rgb.shape[0]):
             a = (rgb[i].clip(0, 1).reshape(wh[1], wh[0], 3) * 255).byte().cpu().numpy()
             Image.fromarray(a).save(os.path.join(args.out, f"{i:03d}.png"))
+    if args.light_turntable:
+        rec.update(light_turntable(nerf, rays[:1], focal, chunk, noise, args.light_turntable, wh, args.out))
     if args.eval_dir:
         from .renderer import evaluation
         from .train import test_all_record
