@@ -1157,11 +1157,64 @@ void vm_pack_density_into(int64_t p_addr, const std::vector<Tensor>& planes, con
 
 }  // namespace
 
+namespace {
+
+// ---- what the timing bindings share ----------------------------------------------------------------------------------------
+// takes `timer` over (and frees it), waits for each recorded call and hands the record to fn
+template <class F>
+void drain_timer(CallTimer*& timer, F fn) {
+    std::unique_ptr<CallTimer> t(timer);
+    timer = nullptr;
+    if (!t) return;
+    for (auto& r : t->recs) {
+        check(nmf_event_synchronize(r.b), "nmf_event_synchronize");
+        fn(r, t->recs[0]);
+    }
+}
+float ms_between(void* a, void* b) {
+    float ms = 0.f;
+    check(nmf_event_elapsed_ms(a, b, &ms), "nmf_event_elapsed_ms");
+    return ms;
+}
+// -> {key: (summed ms, records)} over the records of `timer`; keys(record) names the sums a record enters
+template <class F>
+py::dict timer_sums(CallTimer*& timer, F keys) {
+    std::map<std::string, std::pair<double, int64_t>> acc;
+    drain_timer(timer, [&](const CallTimer::Rec& r, const CallTimer::Rec&) {
+        const float ms = ms_between(r.a, r.b);
+        for (const std::string& k : keys(r)) {
+            acc[k].first += ms;
+            acc[k].second += 1;
+        }
+    });
+    py::dict out;
+    for (auto& kv : acc) out[py::str(kv.first)] = py::make_tuple(kv.second.first, kv.second.second);
+    return out;
+}
+
+PyObject* g_unsupported_class = nullptr;   // nmf_amd.fast_step.Unsupported
+
+}  // namespace
+
 PYBIND11_MODULE(_nmf_host, m) {
     m.doc() = "host-side fast path of nmf_amd.hip (same C ABI underneath)";
     m.def("set_error_class", [](py::object cls) {
         g_error_class = cls.ptr();
         Py_XINCREF(g_error_class);
+    });
+    // StepCore's "this chunk is outside the fused pass" (UnsupportedChunk) as the Python class registered here; any other
+    // exception keeps pybind's translation (std::runtime_error -> RuntimeError, a raised Python exception -> itself)
+    m.def("set_unsupported_class", [](py::object cls) {
+        g_unsupported_class = cls.ptr();
+        Py_XINCREF(g_unsupported_class);
+    });
+    m.def("unsupported_class", []() { return g_unsupported_class ? py::reinterpret_borrow<py::object>(g_unsupported_class) : py::object(py::none()); });
+    py::register_local_exception_translator([](std::exception_ptr p) {
+        try {
+            if (p) std::rethrow_exception(p);
+        } catch (const UnsupportedChunk& e) {
+            PyErr_SetString(g_unsupported_class ? g_unsupported_class : PyExc_RuntimeError, e.what());
+        }
     });
     m.def("abi_version", []() { return (int)NMF_ABI_VERSION; });     // what THIS module was compiled against (hip.py compares)
     m.def("call_timing_begin", [](const std::string& only) {
@@ -1171,22 +1224,7 @@ PYBIND11_MODULE(_nmf_host, m) {
         g_call_filter = only;
     }, py::arg("only") = "");
     m.def("call_timing_end", []() {        // waits for the recorded work; -> {name: (ms, calls)}
-        py::dict out;
-        if (!g_call_timer) return out;
-        CallTimer* t = g_call_timer;
-        g_call_timer = nullptr;
-        std::map<std::string, std::pair<double, int64_t>> acc;
-        for (auto& r : t->recs) {
-            float ms = 0.f;
-            check(nmf_event_synchronize(r.b), "nmf_event_synchronize");
-            check(nmf_event_elapsed_ms(r.a, r.b, &ms), "nmf_event_elapsed_ms");
-            auto& e = acc[r.name];
-            e.first += ms;
-            e.second += 1;
-        }
-        for (auto& kv : acc) out[py::str(kv.first)] = py::make_tuple(kv.second.first, kv.second.second);
-        delete t;
-        return out;
+        return timer_sums(g_call_timer, [](const CallTimer::Rec& r) { return std::vector<std::string>{r.name}; });
     });
     m.def("kernel_timing_begin", [](const std::string& only, bool by_stream) {
         g_kernel_by_stream = by_stream;
@@ -1198,32 +1236,13 @@ PYBIND11_MODULE(_nmf_host, m) {
         check(nmf_set_launch_probe(&launch_probe), "nmf_set_launch_probe");
     }, py::arg("only") = "", py::arg("by_stream") = false);
     m.def("kernel_timing_end", []() {      // waits for the recorded work; -> {kernel: (ms, launches)}
-        py::dict out;
         check(nmf_set_launch_probe(nullptr), "nmf_set_launch_probe");
-        if (!g_kernel_timer) return out;
-        CallTimer* t = g_kernel_timer;
-        g_kernel_timer = nullptr;
-        std::map<std::string, std::pair<double, int64_t>> acc;
-        for (auto& r : t->recs) {
-            float ms = 0.f;
-            check(nmf_event_synchronize(r.b), "nmf_event_synchronize");
-            check(nmf_event_elapsed_ms(r.a, r.b, &ms), "nmf_event_elapsed_ms");
-            auto& e = acc[kernel_name(r.name)];
-            e.first += ms;
-            e.second += 1;
+        return timer_sums(g_kernel_timer, [](const CallTimer::Rec& r) {
             const std::string sid = "@" + std::to_string(reinterpret_cast<int64_t>(r.stream));
-            auto& q = acc[sid];      // per-stream sums (the main stream = the chain) ...
-            q.first += ms;
-            q.second += 1;
-            if (g_kernel_by_stream) {      // ... and per kernel and stream
-                auto& w = acc[kernel_name(r.name) + sid];
-                w.first += ms;
-                w.second += 1;
-            }
-        }
-        for (auto& kv : acc) out[py::str(kv.first)] = py::make_tuple(kv.second.first, kv.second.second);
-        delete t;
-        return out;
+            std::vector<std::string> keys = {kernel_name(r.name), sid};      // per kernel; per stream (the main stream = the chain) ...
+            if (g_kernel_by_stream) keys.push_back(kernel_name(r.name) + sid);      // ... and per kernel and stream
+            return keys;
+        });
     });
     m.def("readback_wait_us", [](bool reset) { const double w = SizeReadback::waited_us(); if (reset) SizeReadback::waited_us() = 0.0; return w; });
     m.def("readback_wait_by_slot_us", [](bool reset) {
@@ -1234,21 +1253,10 @@ PYBIND11_MODULE(_nmf_host, m) {
     m.def("set_call_delay", [](const std::string& name, double us) { g_delay_name = name; g_delay_us = us; });
     m.def("call_timing_timeline", []() {   // waits for the recorded work; -> [(name, stream, start_us, end_us, host_issue_us)], times
         py::list out;                      // relative to the first recorded call (device clock / host clock)
-        if (!g_call_timer) return out;
-        CallTimer* t = g_call_timer;
-        g_call_timer = nullptr;
-        if (!t->recs.empty()) {
-            void* ref = t->recs[0].a;
-            const double h0 = t->recs[0].host_us;
-            for (auto& r : t->recs) {
-                float s_ms = 0.f, e_ms = 0.f;
-                check(nmf_event_synchronize(r.b), "nmf_event_synchronize");
-                check(nmf_event_elapsed_ms(ref, r.a, &s_ms), "nmf_event_elapsed_ms");
-                check(nmf_event_elapsed_ms(ref, r.b, &e_ms), "nmf_event_elapsed_ms");
-                out.append(py::make_tuple(std::string(r.name), reinterpret_cast<int64_t>(r.stream), 1e3 * s_ms, 1e3 * e_ms, r.host_us - h0));
-            }
-        }
-        delete t;
+        drain_timer(g_call_timer, [&](const CallTimer::Rec& r, const CallTimer::Rec& first) {
+            out.append(py::make_tuple(std::string(r.name), reinterpret_cast<int64_t>(r.stream), 1e3 * ms_between(first.a, r.a),
+                                      1e3 * ms_between(first.a, r.b), r.host_us - first.host_us));
+        });
         return out;
     });
     m.def("march_count", &march_count);
@@ -1328,11 +1336,10 @@ PYBIND11_MODULE(_nmf_host, m) {
         .def("train_forward", &StepCore::train_forward)
         .def("train_backward", &StepCore::train_backward)
         .def("has_pending", &StepCore::has_pending)
-        .def("drop_pending", &StepCore::drop_pending)
         .def("render", &StepCore::render, py::arg("rays"), py::arg("focal"), py::arg("noise"), py::arg("want_maps"),
              py::arg("want_materials") = false)
         .def("begin_step", &StepCore::begin_step)
-        .def("join_early_env", &StepCore::join_early_env)
+        .def("join_env_table_backward", &StepCore::join_env_table_backward)
         .def("env_was_used", &StepCore::env_was_used)
         .def("env_table_backward_queued", &StepCore::env_table_backward_queued)
 #define RW(name) .def_readwrite(#name, &StepCore::name)

@@ -1,6 +1,6 @@
-// The training / evaluation pass of nmf_amd/fast_step.py (TrainPass._fwd / _bwd / chunk / _flush_walks / render_chunk) as ONE
-// C++ call per chunk: the same C-ABI calls in the same order, issued from C++ instead of from ~150 Python wrapper calls.
-// Included by host_ext.cpp (same namespace: it calls that file's wrappers directly).
+// The training / evaluation pass of nmf_amd/fast_step.py (TrainPass.chunk / forward_autograd + backward_autograd / render_chunk) as
+// ONE C++ call per chunk and direction: the C-ABI calls of a chunk in order, issued from C++ instead of from ~150 Python wrapper
+// calls.  Included by host_ext.cpp (same namespace: it calls that file's wrappers directly).
 //
 // Why: in the regimes where a chunk has little device work (level 0 of every step, the early phase with 1000 re-traced rays,
 // evaluation chunks, the 300^3 grid where the sample budget keeps ~2200 rays) the step was bound by the ~15 us of Python per
@@ -12,6 +12,11 @@
 //
 // The noise source and the replayed bookkeeping (noise.Pins) are Python objects called back through pybind: DeviceNoise
 // answers from its pools in ~2 us, ReplayNoise / Pins (tests: the reference's fixtures run through THIS code) may be slow.
+//
+// A chunk OUTSIDE the pass (no bounce row, no secondary sample, maps without dense normals) throws UnsupportedChunk, which Python
+// sees as nmf_amd.fast_step.Unsupported (host_ext.cpp: set_unsupported_class); every other error keeps its own type.
+
+struct UnsupportedChunk : std::runtime_error { using std::runtime_error::runtime_error; };
 
 struct RuntimeEvent {
     void* ev = nullptr;
@@ -59,7 +64,6 @@ struct SizeReadback {
     }
 };
 
-struct SizeReadback;
 struct CoreSamples {
     Tensor xyzt, ray_id, step_id, dist, offsets, whole_valid, rays, valid;
     OT jitter, z;
@@ -170,7 +174,6 @@ class StepCore {
         return out;
     }
     bool has_pending() const { return (bool)pending_; }
-    void drop_pending() { pending_.reset(); pending_keep_.clear(); }
     // d_acc / d_ori: adjoints of the per-ray accumulated opacity and orientation terms (None: zero).  last: every environment
     // adjoint of the optimizer step has been queued with this chunk -- the env-map table backward then starts on its side stream
     void train_backward(const Tensor& d_rgb, const OT& d_acc, const OT& d_ori, bool last) {
@@ -237,8 +240,9 @@ class StepCore {
     // want_maps: also the two per-ray maps of the reference's evaluation branch that need no dense appearance pass
     // (modules/tensor_nerf.py:480-501): depth = sum_k w_k z_k, world_normal = acc * sum_k w_k n_k + (1 - acc)
     // want_materials: also the material maps of level 0 (renderer.py:440-463) as one [B,15] block (nmf_material_maps: albedo |
-    // roughness | diffuse | tint | spec), appended last.  Queued after the whole level tree: the appearance query over all kept
+    // roughness | diffuse | tint | spec).  Queued after the whole level tree: the appearance query over all kept
     // samples, then one launch; no noise is drawn and no launch the other outputs come from changes.
+    // -> dict(rgb_map, acc, kept, n_samples, [depth, world_normal], [materials]), or None when the sampler kept no sample
     py::object render(const Tensor& rays, double focal, py::object noise, bool want_maps, bool want_materials = false) {
         begin(noise);
         eval_z_ = want_maps;
@@ -251,19 +255,20 @@ class StepCore {
         }
         eval_z_ = false;
         if (t->M == 0) return py::none();
-        OT mats;
-        if (want_materials) mats = material_maps_(*t);
-        if (!want_maps) {
-            if (mats.has_value()) return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples, *mats);
-            return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples);
+        py::dict out;
+        out["rgb_map"] = t->rgb_map;
+        out["acc"] = t->acc;
+        out["kept"] = t->B;
+        out["n_samples"] = t->n_samples;
+        if (want_materials) out["materials"] = material_maps_(*t);
+        if (want_maps) {
+            if (!t->S.z.has_value() || !t->nr.has_value()) throw UnsupportedChunk("evaluation maps need the sampler's z values and dense normals");
+            out["depth"] = segment_sum(t->S.z->view({t->M, 1}), OT(t->w), t->offsets, t->B, 1, main_stream).view({t->B});
+            Tensor wn = segment_sum(*t->nr, OT(t->w), t->offsets, t->B, 1, main_stream);
+            Tensor a = t->acc.unsqueeze(1);
+            out["world_normal"] = a * wn + (1.0 - a);
         }
-        if (!t->S.z.has_value() || !t->nr.has_value()) throw std::runtime_error("Unsupported: evaluation maps need the sampler's z values and dense normals");
-        Tensor depth = segment_sum(t->S.z->view({t->M, 1}), OT(t->w), t->offsets, t->B, 1, main_stream).view({t->B});
-        Tensor wn = segment_sum(*t->nr, OT(t->w), t->offsets, t->B, 1, main_stream);
-        Tensor a = t->acc.unsqueeze(1);
-        Tensor world_normal = a * wn + (1.0 - a);
-        if (mats.has_value()) return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples, depth, world_normal, *mats);
-        return py::make_tuple(t->rgb_map, t->acc, t->B, t->n_samples, depth, world_normal);
+        return out;
     }
 
   private:
@@ -271,9 +276,9 @@ class StepCore {
     // nmf_material_maps over the samples, their dense normals and the level's bounce rows
     Tensor material_maps_(CoreLevel& t) {
         if (!t.nr.has_value() || t.sparse_n || t.lvl != 0)
-            throw std::runtime_error("Unsupported: material maps need the dense normals of level 0");
+            throw UnsupportedChunk("material maps need the dense normals of level 0");
         if (!t.brdf.has_value() || !t.incoming.defined() || t.incoming.size(0) != t.R || !t.conv.defined() || !head_W.defined())
-            throw std::runtime_error("Unsupported: material maps need the bounce rows' incoming radiance and BRDF weights");
+            throw UnsupportedChunk("material maps need the bounce rows' incoming radiance and BRDF weights");
         const int64_t M = t.M, B = t.B;
         Tensor xyzt = t.S.xyzt.narrow(0, 0, M).contiguous();
         Tensor app = *std::get<4>(vm_query_fwd(vm_p, xyzt, fw(f_dpk, dpk), fw(f_dlk, dlk), fw(f_apl, apl), fw(f_ali, ali), basis, false,
@@ -431,8 +436,7 @@ class StepCore {
         return *dd;
     }
 
-    static Tensor to_tensor(const py::object& o) { return o.cast<Tensor>(); }
-    Tensor uniform(py::object& noise, std::vector<int64_t> shape) { return to_tensor(noise.attr("uniform")(py::tuple(py::cast(shape)))); }
+    Tensor uniform(py::object& noise, std::vector<int64_t> shape) { return noise.attr("uniform")(py::tuple(py::cast(shape))).cast<Tensor>(); }
     void skip(py::object& noise, const char* kind, std::vector<int64_t> shape) { noise.attr("skip")(kind, py::tuple(py::cast(shape))); }
     void trace_put(const std::string& key, const Tensor& t) {
         if (trace_.is_none()) return;
@@ -479,18 +483,6 @@ class StepCore {
     // composite may run over all rays; the queries behind them read the count from the device
     CoreSamples sample_finish(Pending& P, py::object& sampler, bool live = false) {
         CoreSamples S;
-        if (live && P.rb != nullptr) {
-            const int64_t B0 = P.rays.size(0);
-            const int64_t Mc = std::min<int64_t>(max_samples, B0 * P.N);
-            OT z;
-            std::tie(S.xyzt, S.ray_id, S.step_id, z, S.dist) =
-                march_fill(reinterpret_cast<int64_t>(&P.p), P.rays, B0, Mc, P.jitter, P.valid, P.offsets, false, main_stream);
-            S.offsets = P.offsets; S.whole_valid = P.wv.view(at::kBool); S.rays = P.rays; S.valid = P.valid; S.jitter = P.jitter;
-            S.M = Mc; S.b = B0; S.N = P.N;
-            S.live = reinterpret_cast<int64_t>(P.totals.data_ptr());
-            S.live_rb = P.rb;
-            return S;
-        }
         if (P.rb == nullptr) {
             py::object s = sampler.attr("sample_finish")(P.py_pending);
             S.xyzt = s.attr("xyzt").cast<Tensor>(); S.ray_id = s.attr("ray_id").cast<Tensor>(); S.step_id = s.attr("step_id").cast<Tensor>();
@@ -500,9 +492,17 @@ class StepCore {
             S.M = s.attr("M").cast<int64_t>(); S.b = s.attr("b").cast<int64_t>(); S.N = s.attr("N").cast<int64_t>();
             return S;
         }
-        auto [M, b] = P.rb->get();
+        int64_t M, b;
+        if (live) {
+            b = P.rays.size(0);
+            M = std::min<int64_t>(max_samples, b * P.N);
+            S.live = reinterpret_cast<int64_t>(P.totals.data_ptr());
+            S.live_rb = P.rb;
+        } else {
+            std::tie(M, b) = P.rb->get();
+        }
         std::tie(S.xyzt, S.ray_id, S.step_id, S.z, S.dist) =
-            march_fill(reinterpret_cast<int64_t>(&P.p), P.rays, b, M, P.jitter, P.valid, P.offsets, eval_z_, main_stream);
+            march_fill(reinterpret_cast<int64_t>(&P.p), P.rays, b, M, P.jitter, P.valid, P.offsets, !live && eval_z_, main_stream);
         S.offsets = P.offsets; S.whole_valid = P.wv.view(at::kBool); S.rays = P.rays; S.valid = P.valid; S.jitter = P.jitter;
         S.M = M; S.b = b; S.N = P.N;
         return S;
@@ -628,7 +628,7 @@ class StepCore {
         }
         if (R == 0) {
             env_ready();
-            throw std::runtime_error("Unsupported: no bounce rows");
+            throw UnsupportedChunk("no bounce rows");
         }
         t->R = R; t->Mb = Mb;
         t->bidx = t->bidx.narrow(0, 0, Mb); t->row_off = t->row_off.narrow(0, 0, Mb + 1); t->cnt32 = t->cnt32.narrow(0, 0, Mb);
@@ -670,7 +670,7 @@ class StepCore {
             if (full_retrace) {
                 skip(noise, "rand", {R});
                 t->child = fwd(lvl + 1, t->brays, focal, t->mip, noise, is_train, mlp);     // the MLP runs under the child's read-back
-                if (t->child->M == 0) throw std::runtime_error("Unsupported: no secondary sample");
+                if (t->child->M == 0) throw UnsupportedChunk("no secondary sample");
                 t->n_samples.insert(t->n_samples.end(), t->child->n_samples.begin(), t->child->n_samples.end());
                 t->incoming = t->child->rgb_map;
             } else {
@@ -689,10 +689,8 @@ class StepCore {
                 } else {
                     Tensor order = argsort_(cc.contiguous()).to(at::kLong);
                     trace_put("retrace_order_own" + std::to_string(lvl), order);
-                    if (!pins_.is_none()) {
-                        py::dict ro = pins_.attr("retrace_order").cast<py::dict>();
-                        if (ro.contains(py::int_(lvl))) order = ro[py::int_(lvl)].cast<Tensor>().to(order.device());
-                    }
+                    py::dict ro = pins_.attr("retrace_order").cast<py::dict>();
+                    if (ro.contains(py::int_(lvl))) order = ro[py::int_(lvl)].cast<Tensor>().to(order.device());
                     t->idx_re = order.narrow(0, cut, R - cut);
                     t->idx_no = order.narrow(0, 0, cut);
                     trace_put("retrace_score" + std::to_string(lvl), cc);
@@ -704,7 +702,7 @@ class StepCore {
                     t->brays_re = at::index_select(t->brays, 0, *t->idx_re);
                     t->mip_re = at::index_select(t->mip, 0, *t->idx_re);
                     t->child = fwd(lvl + 1, *t->brays_re, focal, t->mip_re, noise, is_train);
-                    if (t->child->M == 0) throw std::runtime_error("Unsupported: no secondary sample");
+                    if (t->child->M == 0) throw UnsupportedChunk("no secondary sample");
                     t->n_samples.insert(t->n_samples.end(), t->child->n_samples.begin(), t->child->n_samples.end());
                     t->incoming.index_copy_(0, *t->idx_re, t->child->rgb_map);
                 }
@@ -886,8 +884,8 @@ class StepCore {
                                       rows6.slice(1, 3, 6), d_feat, t.app, head_W, head_b, head_p, g_hW, g_hb, main_stream);
         } else {
             std::tie(d_normals, d_heads, d_app) =
-                bounce_prep_bwd(t.sparse_n ? OT() : OT(t.inv), *t.nr, t.heads, S.ray_id, S.rays, t.conv, min_rough, detach_n, dN, dr1,
-                                rows6.slice(1, 0, 3), rows6.slice(1, 3, 6), d_feat, t.bidx, t.sparse_n ? 2 : 1, main_stream);
+                bounce_prep_bwd(OT(t.inv), *t.nr, t.heads, S.ray_id, S.rays, t.conv, min_rough, detach_n, dN, dr1,
+                                rows6.slice(1, 0, 3), rows6.slice(1, 3, 6), d_feat, t.bidx, 1, main_stream);
             d_app = heads_bwd(t.app, head_W, head_b, head_p, d_heads, g_hW, g_hb, OT(d_app), main_stream);
         }
         app_segs_.push_back(Seg(t.xyz_rows, OT(), OT(), OT(), OT(), OT(), d_app));
@@ -922,7 +920,7 @@ class StepCore {
 
   public:
     // end_step: the main stream waits for the env-map table backward queued on the side stream
-    void join_early_env() {
+    void join_env_table_backward() {
         if (early_env_done && early_env_side_) join(early_env_side_);
         early_env_done = false;
         early_env_side_ = 0;

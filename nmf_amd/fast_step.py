@@ -12,8 +12,11 @@ accumulator, and the conversion of the accumulators into parameter gradients.  I
     the reference's own training loop (train.py:509-747: forward, torch loss, `total_loss.backward()`, `optimizer.step()`).
 
 Scope: is_train=True (or the forward-only evaluation render), the sparse-appearance path (no debug maps), recursion depth
-len(max_retrace_rays) <= 1.  Anything else raises Unsupported BEFORE touching an accumulator and the
-caller runs that chunk through the autograd operator graph of nmf_amd/functional.py (tests/test_hip_e2e.py compares the two).
+len(max_retrace_rays) <= 1.  Anything else raises `Unsupported` (here, or in the C++ pass, whose exception type for it is registered
+as this class) BEFORE touching an accumulator and the caller runs that chunk through the autograd operator graph of
+nmf_amd/functional.py (tests/test_hip_e2e.py compares the two); any other exception of a chunk reaches the caller as it is.
+Every call into the C++ pass sits in one bracket (`TrainPass._pass`), the step's gradients are named by one table (`_grad_table`),
+and the env-map table backward of a step has one state, on the step's accumulator set (`_env_reported` ... `_finish_grads`).
 Replayed bookkeeping of a reference run (noise.Pins on a ReplayNoise: bounce counts, re-trace order, occupancy decisions) is honoured
 by the C++ pass, so the reference's full-size fixtures are checked on THIS path (tests/test_hip_timed_path.py).
 Reference spans are the ones cited in functional.py for each call.  (Rounds 2-4 kept a Python twin of the C++ pass in this file; it was
@@ -29,7 +32,26 @@ from . import hip
 
 
 class Unsupported(Exception):
-    pass
+    """this chunk is outside the fused pass: the caller runs it through the operator graph"""
+
+
+hip.HOST_EXT.set_unsupported_class(Unsupported)       # what StepCore throws for such a chunk (csrc/step_core.inc: UnsupportedChunk)
+
+
+def module_pass(nerf, call):
+    """-> call(), between begin_pass() and end_pass() of every module that keeps state for one pass (gradient-pass tokens, memoised
+    tables): one fused chunk, or one forward of the module path (TensorNeRF.forward).  A plain function, no context manager: it is
+    on the host's critical path once per chunk (a generator-based one measured 3-7 us per chunk, of a 1.36 ms step)"""
+    model = nerf.model
+    mods = [m for m in (nerf.rf, nerf.bg_module, getattr(model, "brdf", None), getattr(model, "diffuse_module", None))
+            if hasattr(m, "begin_pass")]
+    for m in mods:
+        m.begin_pass()
+    try:
+        return call()
+    finally:
+        for m in mods:
+            m.end_pass()
 
 
 MLP_SIDE_MIN_RAYS = 100000   # the capped launch runs at about half speed: it pays only next to enough other work, i.e. when the
@@ -47,6 +69,10 @@ MLP_SIDE_WGS = 192      # persistent workgroups of a BRDF-MLP backward that shar
                         # workgroup of 4 waves and 150 KB of LDS per CU): in-process A/B 32: 1.812 ms, 64: 1.628, 96: 1.608,
                         # 128: 1.625, 192: 1.678, 256: 1.696 -- the launch is short now, and every CU it occupies is a CU whose
                         # LDS the kernels of the main stream cannot use (round 2, fp32 kernel: 192 / 256 best)
+
+
+HEAD_ROWS = ((0, 3), (3, 6), (6, 9), (9, 11))   # rows of the stacked material heads: diffuse, tint, f0, roughness
+ENV_NOT_RUN, ENV_QUEUED, ENV_DONE = "not run", "queued", "done"      # the env-map table backward of a step (accumulator set: env_bwd)
 
 
 # Chunk contexts: the chunks of ONE optimizer step are independent given the parameters (the reference runs them one after another,
@@ -110,18 +136,15 @@ class TrainPass:
         # gain), the composite backward on a side stream (2.25 ms); anything of the FORWARD on a side stream (the MLP next to the
         # level-1 sampler: 2.36 ms, the background lookup of the secondary rays next to it: 2.28 ms).  NMF_OVERLAP=0 keeps everything on one stream.
         self.overlap = os.environ.get("NMF_OVERLAP", "1") != "0"
-        self._last_chunk = False
         self._acc_cache = None
         self._owner_slots = None
         self.sparse_normals = os.environ.get("NMF_SPARSE_NORMALS", "1") != "0"
-        self._early_env = None
         # Side streams are PROCESS-WIDE, one per role and device: HIP maps streams onto a few hardware queues in creation
         # order (GPU_MAX_HW_QUEUES, 4 by default), and which roles end up sharing a queue decides what can overlap.  With
         # streams of its own, the second, third, ... TrainPass of a process got another role -> queue assignment than the
         # first and ran up to 0.25 ms per step slower (tools/model_order_check.py); passes of one process run one after the
         # other, so they can share the streams.
         self._side = _SIDE_STREAMS.setdefault(torch.cuda.current_device() if torch.cuda.is_available() else -1, {})
-        self._main = None
         self._ctxs = []                 # chunk contexts: _ns(index, core, main (torch Stream; None = torch's current stream), ...)
         self._ctx_used = []             # contexts with chunks of the running optimizer step in flight
         self._switches = {}
@@ -170,15 +193,19 @@ class TrainPass:
         """-> lib/_nmf_host.so's StepCore of chunk context i, configured for this model"""
         return self.context(i).core
 
-    def cores(self):
-        return [cx.core for cx in self._ctxs]
-
     def set_switch(self, name, value):
         """a boolean switch of the C++ pass (env_split, ...: A/B runs and tests) on every chunk context, present and future"""
         self._switches[name] = value
         self.context(0)
         for cx in self._ctxs:
             setattr(cx.core, name, value)
+
+    def comm_stream(self):
+        """the stream the data-parallel trainer runs its early collective on (process-wide, like the other side streams)"""
+        comm = self._side.get("comm")
+        if comm is None:
+            comm = self._side["comm"] = torch.cuda.Stream()
+        return comm
 
     def invalidate_tables(self):
         """a module the derived tables are built from was REPLACED (relight.relit swaps nerf.bg_module): _param_token's cached
@@ -272,7 +299,7 @@ class TrainPass:
             c.sobol = model.brdf_sampler.angs
             c.env_table, c.env_pole, c.env_act = bgm._cache[1][3], env[2], env[0]
             c.env_bg = bgm.bg_mat.detach().reshape(3, bgm.bg_mat.shape[-2], bgm.bg_mat.shape[-1])
-            c.white, c.one = _white(dev), _one(dev)
+            c.one = _one(dev)
             c.select_ws = hip.select_total_workspace(dev, main)          # (one per stream: chunks of two contexts overlap)
             c.scale = float(rf.distance_scale)
             c.max_brdf_rays = [int(v) for v in model.max_brdf_rays]
@@ -337,56 +364,84 @@ class TrainPass:
         if mr != cx.retrace:
             cx.retrace = mr
             c.max_retrace_rays = mr
-        return c
+
+    def _pass(self, call, dev, focal, is_train, bg, cx=None):
+        """the bracket of every call into the C++ pass: -> call(StepCore of chunk context `cx`, default 0), run with what the core
+        reads in place -- the modules inside their pass, tables and per-chunk values (_core_sync), the background colour `bg` [1,3]
+        of the primary rays.  Raises Unsupported for a configuration outside the pass.  Host work only: nothing is queued or waited for."""
+        if not self.supported():
+            raise Unsupported("configuration")
+        cx = cx if cx is not None else self.context(0)
+
+        def run():
+            self._core_sync(dev, focal, is_train, cx)
+            cx.core.white = bg
+            return call(cx.core)
+        return module_pass(self.nerf, run)
 
     def _core_chunk(self, cx, rays, gt, focal, noise, inv_lbatch, wts, want_total, last):
-        c = cx.core
         rf = self.nerf.rf
         dev = rays.device
-        mods = [m for m in (rf, self.nerf.bg_module, self.nerf.model.brdf, self.nerf.model.diffuse_module) if hasattr(m, "begin_pass")]
-        for m in mods:
-            m.begin_pass()
-        try:
-            self._core_sync(dev, focal, True, cx)
-            c.white = _white(dev)
+
+        def run(c):
             a = self._accumulators(dev)
             self._bind_accumulators(cx, a)
-            c.used_env = bool(a.used_env)
+            c.used_env = a.used_env
 
             def total_of(loss, ori, acc):
                 dens = list(rf.density_rf.app_plane) + list(rf.density_rf.app_line)
                 l1 = hip.l1_mean_fwd([x.detach() for x in dens])
                 return hip.loss_mix_fwd([loss, l1, ori, acc], wts, inv_lbatch)
 
-            try:
-                out = c.chunk(rays, gt, float(focal), noise, float(inv_lbatch), [float(w) for w in wts], bool(want_total), bool(last),
-                              total_of)
-            except RuntimeError as e:
-                if "Unsupported" in str(e):
-                    raise Unsupported(str(e)) from None
-                raise
-            a.used_env = bool(a.used_env) or bool(c.env_was_used())
-            if c.env_table_backward_queued():
-                self._early_env = (c, a.d_bg)
+            out = c.chunk(rays, gt, float(focal), noise, float(inv_lbatch), [float(w) for w in wts], bool(want_total), bool(last),
+                          total_of)
+            self._env_reported(a, c)
             if out["loss"] is None:
                 return dict(loss=None, kept=out["kept"], n_samples=[0])
-            pins = getattr(noise, "pins", None)
-            if pins is not None and pins.trace is not None:
-                pass                                  # (the C++ pass wrote rgb_map0 / acc_map0 / whole_valid0 ... itself)
             self.n_loss_chunks += 1
             self.l1_scale += float(wts[1]) * float(inv_lbatch)
-            self.last_sizes = dict(rays=int(out["kept"]), n_samples=list(out["n_samples"]), n_rays=list(out["n_rays"]),
-                                   n_rows=list(out["n_rows"]))
+            self._sizes_of(out)
             return dict(loss=out["loss"], total=out["total"], kept=out["kept"], n_samples=list(out["n_samples"]))
-        finally:
-            for m in mods:
-                m.end_pass()
+        return self._pass(run, dev, focal, True, _white(dev), cx)
+
+    def _sizes_of(self, out):
+        self.last_sizes = dict(rays=int(out["kept"]), n_samples=list(out["n_samples"]), n_rays=list(out["n_rays"]),
+                               n_rows=list(out["n_rows"]))
+
+    # ---- the env-map table backward of the step: d_sat, d_pole -> d_bg, once, behind the step's last env-map adjoint ------------
+    # The state lives on the step's accumulator set: `used_env` (a chunk of the step looked the map up) and `env_bwd` = ENV_NOT_RUN,
+    # ENV_QUEUED (by StepCore `env_core`, in its last chunk's backward, on its side stream) or ENV_DONE (d_bg holds the result).
+    @staticmethod
+    def _env_reset(a):
+        a.used_env, a.env_bwd, a.env_core = False, ENV_NOT_RUN, None
+
+    @staticmethod
+    def _env_reported(a, c):
+        """behind a backward of StepCore `c` (or from inside it: the early callback), which was handed a.used_env: what it reports"""
+        a.used_env = a.used_env or bool(c.env_was_used())
+        if c.env_table_backward_queued():
+            a.env_bwd, a.env_core = ENV_QUEUED, c
+
+    @staticmethod
+    def _env_join(a):
+        """d_bg is about to be read: the main stream of the core that queued the table backward waits for it.  -> True if one was queued"""
+        if a.env_bwd != ENV_QUEUED:
+            return False
+        a.env_core.join_env_table_backward()
+        a.env_bwd, a.env_core = ENV_DONE, None
+        return True
+
+    def _env_run(self, a, keep_sat=False):
+        """the table backward on the current stream (it destroys the adjoint table it reads: keep_sat runs it on a copy)"""
+        bgm = self.nerf.bg_module
+        act, _sat, _pole = bgm._tables()
+        hip.sat_build_bwd(a.d_sat.clone() if keep_sat else a.d_sat, bgm.bg_mat.detach(), act, a.d_pole, sc=bgm._dev_scalars(), out=a.d_bg)
+        a.env_bwd = ENV_DONE
 
     # ---- accumulators of one optimizer step ------------------------------------------------------------------------
     def begin_step(self):
         self.acc = None
         self._acc_empty = False
-        self._early_env = None
         self.n_loss_chunks = 0
         self.l1_scale = 0.0
         self._ctx_used = []
@@ -436,13 +491,13 @@ class TrainPass:
             gl = [t.view(1, G, 1, 16).permute(0, 3, 1, 2) for t in v[9:12]]     # [1,16,G,1] over [G][16]
             c = _ns(key=key, flat=flat, g_dpk=v[0:3], g_dlk=v[3:6], gp=gp, gl=gl, g_apl=v[12:15], g_ali=v[15:18], g_basis=v[18],
                     tail=v[19], g_mlp=v[20:26], g_hW=v[26], g_hb=v[27], d_mip=v[28], d_bg=v[29], d_sat=v[30], d_pole=v[31],
-                    late=flat[offs[6]:offs[20]], early=flat[offs[20]:offs[30]], used_env=False,
-                    pairs=None, d_bg_view=None, l1=None, l1_dev=None, early_pairs=None)
+                    late=flat[offs[6]:offs[20]], early=flat[offs[20]:offs[30]], used_env=False, env_bwd=ENV_NOT_RUN, env_core=None,
+                    table=None, pairs=None, early_pairs=None, d_bg_view=None, l1=None, l1_dev=None)
             self._acc_cache = c
             self._delivered = None
         if zero:
             c.flat.zero_()
-            c.used_env = False
+            self._env_reset(c)
             self.acc = c
         return c
 
@@ -455,32 +510,17 @@ class TrainPass:
         {albedo, roughness, diffuse, tint, spec} of [b,3] maps with want_materials (level 0, renderer.py:440-463: one appearance query
         over the kept samples and nmf_material_maps, queued after everything else; the other outputs keep their bits).  Raises
         Unsupported (configuration, no sample, no bounce row): the caller renders that chunk through the module."""
-        nerf = self.nerf
-        if not self.supported():
-            raise Unsupported("configuration")
-        mods = [m for m in (nerf.rf, nerf.bg_module, nerf.model.brdf, nerf.model.diffuse_module) if hasattr(m, "begin_pass")]
-        for m in mods:
-            m.begin_pass()
-        try:
-            core = self.core()
-            self._core_sync(rays.device, focal, False)
-            try:
-                out = core.render(rays, float(focal), noise, bool(want_maps), bool(want_materials))
-            except RuntimeError as e:
-                if "Unsupported" in str(e):
-                    raise Unsupported(str(e)) from None
-                raise
-            if out is None:
-                raise Unsupported("no sample")
-            res = (out[0], out[1], out[2], list(out[3])) + ((out[4], out[5]) if want_maps else ())
-            if want_materials:
-                from .hip import MATERIAL_MAPS
-                block = out[-1]
-                res = res + ({k: block[:, 3 * i:3 * i + 3] for i, k in enumerate(MATERIAL_MAPS)},)
-            return res
-        finally:
-            for m in mods:
-                m.end_pass()
+        out = self._pass(lambda core: core.render(rays, float(focal), noise, bool(want_maps), bool(want_materials)),
+                         rays.device, focal, False, _white(rays.device))
+        if out is None:
+            raise Unsupported("no sample")
+        res = (out["rgb_map"], out["acc"], out["kept"], list(out["n_samples"]))
+        if want_maps:
+            res += (out["depth"], out["world_normal"])
+        if want_materials:
+            block = out["materials"]
+            res += ({k: block[:, 3 * i:3 * i + 3] for i, k in enumerate(hip.MATERIAL_MAPS)},)
+        return res
 
     # ---- one chunk: forward, loss, backward (nmf_amd.trainer.Trainer) ------------------------------------------------------
     @torch.no_grad()
@@ -488,12 +528,15 @@ class TrainPass:
         """wts = (w_photo, w_l1, w_ori, w_acc).  Returns dict(loss 0-d tensor, kept, n_samples) -- loss None when the chunk
         had no sample (train.py:567-568 skips it).  want_total: also evaluate the chunk's total loss value (the gradients do
         not need it: every term enters linearly with a constant weight)."""
-        if not self.supported():
-            raise Unsupported("configuration")
         cx = self.context(ctx if ctx < self.n_contexts else 0)
         c = cx.core
         # early = (callable, raw comm stream): called from the last chunk's backward when the non-field gradients are final
-        c.early_cb, c.comm_stream = (early[0], int(early[1])) if (early is not None and last) else (None, 0)
+        c.early_cb, c.comm_stream = None, 0
+        if early is not None and last:
+            def early_cb():                       # (from INSIDE the backward: what this core has queued enters the step's state first)
+                self._env_reported(self.acc, c)
+                early[0]()
+            c.early_cb, c.comm_stream = early_cb, int(early[1])
         cur = torch.cuda.current_stream()
         first_use = cx not in self._ctx_used
         if first_use:
@@ -538,20 +581,10 @@ class TrainPass:
             a = self._accumulators(dev)
             self._acc_empty = True
             queued = True
-        cores = self._cores_in_use()
-        used = any(bool(c.env_was_used()) for c in cores) or bool(a.used_env)
-        # (called from inside the last chunk's backward, `_early_env` is not set yet: the cores themselves know what they queued)
-        if used and self._early_env is None and not any(c.env_table_backward_queued() for c in cores):
-            bgm = self.nerf.bg_module
-            act, _sat, _pole = bgm._tables()
-            hip.sat_build_bwd(a.d_sat, bgm.bg_mat.detach(), act, a.d_pole, sc=bgm._dev_scalars(), out=a.d_bg)
-            a.used_env = True
-            self._early_env = ("done", a.d_bg)
+        if a.used_env and a.env_bwd == ENV_NOT_RUN:
+            self._env_run(a)
             queued = True
         return queued
-
-    def _cores_in_use(self):
-        return [cx.core for cx in self._ctxs]
 
     def early_pairs(self, dev):
         """[(parameter, accumulator tensor)] of the BRDF MLP, the material heads and the environment map: what no field walk writes.
@@ -562,18 +595,25 @@ class TrainPass:
         if a is None:                       # (prepare_early opens them in front of the collective's stream dependency)
             a = self._accumulators(dev)
             self._acc_empty = True
-        n = self.nerf
-        bgm = n.bg_module
-        if a.early_pairs is not None:
-            return a.early_pairs
-        m = n.model.brdf.mlp
-        pairs = list(zip((m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias), a.g_mlp))
-        hps = n.model.diffuse_module._head_params()
-        for i, (lo, hi) in enumerate(((0, 3), (3, 6), (6, 9), (9, 11))):
-            pairs += [(hps[2 * i], a.g_hW[lo:hi]), (hps[2 * i + 1], a.g_hb[lo:hi])]
-        pairs += [(bgm.bg_mat, a.d_bg), (bgm.mipbias, a.d_mip)]     # (a step that never looked the env map up: the zeros of the step's fill)
-        a.early_pairs = [(prm, g) for prm, g in pairs if prm.requires_grad]
-        return a.early_pairs
+        return self._grad_table(a)[1]
+
+    def _grad_table(self, a):
+        """[(parameter, accumulator tensor)] of accumulator set `a` (parameters that require a gradient), built once per set, as the
+        two regions of its flat buffer: -> (late, early).  late = the field; early = what no field walk writes: BRDF MLP, material
+        heads, env map (d_bg [3,H,W]: zeros when the step never looked the map up) and mip bias (the fp32 d_mip [1]).  Cached with
+        it: a.early_pairs = early, a.pairs = late + MLP + heads = what .grad takes as it stands (the env entries get reshaped)."""
+        if a.table is None:
+            n = self.nerf
+            rf, bgm = n.rf, n.bg_module
+            late = list(zip(rf._param_list(), rf._grads_to_param_layout(a.gp, a.gl, a.g_apl, a.g_ali, a.g_basis)))
+            shading = list(zip(n.model.brdf._weights(), a.g_mlp))
+            hps = n.model.diffuse_module._head_params()
+            for i, (lo, hi) in enumerate(HEAD_ROWS):
+                shading += [(hps[2 * i], a.g_hW[lo:hi]), (hps[2 * i + 1], a.g_hb[lo:hi])]
+            env = [(bgm.bg_mat, a.d_bg), (bgm.mipbias, a.d_mip)]
+            late, shading, env = ([(prm, g) for prm, g in part if prm.requires_grad] for part in (late, shading, env))
+            a.table, a.pairs, a.early_pairs = (late, shading + env), late + shading, shading + env
+        return a.table
 
     # ---- total-variation terms: once per optimizer step -----------------------------------------------------------------------
     @torch.no_grad()
@@ -597,16 +637,13 @@ class TrainPass:
         the env map's TV gradient is ADDED to the table gradient d_bg the collective sums -> the weighted value (0-d).  The table
         backward of the step has been joined (or run by prepare_early) and is marked done: end_step must not write d_bg again."""
         a = self.acc
-        e = self._early_env
-        if e is not None and e[0] != "done":     # queued by the last chunk's backward on its side stream
-            e[0].join_early_env()
+        if self._env_join(a):                    # queued by the last chunk's backward on its side stream
             self.join_contexts()
         bgm = self.nerf.bg_module
         if bgm.brightness_lr != 0 or bgm.mul_lr != 0:    # (end_step derives their gradients from d_bg, which the TV term is no part of)
             raise NotImplementedError("data-parallel TV_weight_bg with a trainable env-map brightness / mul")
         value, _ = hip.tv_value_grad([bgm.bg_mat], ["env"], [scale], 1.0, grads=[a.d_bg.reshape(bgm.bg_mat.shape)])
-        a.used_env = True
-        self._early_env = ("done", a.d_bg)
+        a.used_env, a.env_bwd = True, ENV_DONE
         return value
 
     def _register_prefetch(self):
@@ -628,11 +665,10 @@ class TrainPass:
         optim.AFTER_STEP.append(cb)
 
     # ---- one chunk as ONE autograd node: what TensorNeRF.forward(is_train=True) returns to a caller that forms its own loss -----
-    def forward_autograd(self, rays, focal, noise):
+    def forward_autograd(self, rays, focal, noise, bg):
         """-> (rgb_map [b,3], acc [b], ori [b], out dict of StepCore.train_forward) with rgb_map / acc / ori attached to a ChunkPass
-        node, or None when the chunk kept no sample.  Raises Unsupported before anything is recorded."""
-        if not self.supported():
-            raise Unsupported("configuration")
+        node, or None when the chunk kept no sample.  bg: the background colour of the primary rays [1,3].  Raises Unsupported
+        before anything is recorded."""
         c = self.core()
         dev = rays.device
         rf = self.nerf.rf
@@ -647,31 +683,20 @@ class TrainPass:
             self._pending = None
         if hasattr(rf, "flush_pending_l1"):
             rf.flush_pending_l1()               # a density_L1 term whose pass never ran its backward
-        mods = [m for m in (rf, self.nerf.bg_module, self.nerf.model.brdf, self.nerf.model.diffuse_module) if hasattr(m, "begin_pass")]
-        for m in mods:
-            m.begin_pass()
-        try:
-            self._core_sync(dev, focal, True)
+
+        def run(c):
             self._bind_accumulators(self.context(0), self._accumulators(dev, zero=False))
             self._fwd_serial += 1
             holder = _ChunkHolder(self._fwd_serial)
-            try:
-                out = c.train_forward(rays.detach(), float(focal), noise)
-            except RuntimeError as e:
-                if "Unsupported" in str(e):
-                    raise Unsupported(str(e)) from None
-                raise
+            out = c.train_forward(rays.detach(), float(focal), noise)
             if list(out["n_samples"]) == [0]:
                 return None
-            self.last_sizes = dict(rays=int(out["kept"]), n_samples=list(out["n_samples"]), n_rays=list(out["n_rays"]),
-                                   n_rows=list(out["n_rows"]))
+            self._sizes_of(out)
             rgb, acc, ori = ChunkPass.apply(self, holder, _token(dev), out["rgb_map"], out["acc"], out["ori"])
             self._pending = (holder.serial, weakref.ref(holder))
             rf._last_holder = holder            # density_L1() of this chunk rides on the node (fields/tensoRF.py)
             return rgb, acc, ori, out
-        finally:
-            for m in mods:
-                m.end_pass()
+        return self._pass(run, dev, focal, True, bg)
 
     def _bind_accumulators(self, cx, a):
         c = cx.core
@@ -702,24 +727,24 @@ class TrainPass:
                 state = "continue"
             elif not all(none):
                 state = "detach"
-        elif any(prm.grad is not None for prm in self._grad_params()):
+        elif any(prm.grad is not None for prm in self._grad_params(a)):
             state = "detach"
         if state == "detach":
             # what this pass had summed so far becomes an ordinary gradient tensor: every .grad that still ALIASES the flat buffer (by
             # address -- a delivered tensor somebody modified in place fails the identity / version test above and is still a view of it)
             lo = a.flat.data_ptr()
             hi = lo + 4 * a.flat.numel()
-            for prm in self._grad_params():
+            for prm in self._grad_params(a):
                 g = prm.grad
                 if g is not None and lo <= g.data_ptr() < hi:
                     prm.grad = g.clone()
         if state != "continue":
             a.flat.zero_()
-            a.used_env = False
+            self._env_reset(a)
             a.l1_dev = None
             c.begin_step()
         self.acc = a
-        c.used_env = bool(a.used_env)
+        c.used_env = a.used_env
         if holder.l1 is not None:               # the chunk's density_L1 term: scale of mean|x| (fields/tensoRF.py:332-340)
             d_l1 = holder.l1[1].reshape(()).float()
             a.l1_dev = d_l1 if a.l1_dev is None else a.l1_dev + d_l1
@@ -732,9 +757,7 @@ class TrainPass:
             c.train_backward(d_rgb, d_acc, d_ori, True)
         finally:
             c.env_keep_sat = False
-        a.used_env = bool(c.env_was_used())
-        if c.env_table_backward_queued():
-            self._early_env = (c, a.d_bg)
+        self._env_reported(a, c)
         grads = self._finish_grads(a, (None if a.l1_dev is None else a.l1_dev), keep_sat=True)
         if state == "detach":
             for prm, g in grads:
@@ -746,10 +769,9 @@ class TrainPass:
             self._delivered = [(prm, g, g._version) for prm, g in grads]
         self.acc = None
 
-    def _grad_params(self):
-        n = self.nerf
-        return (list(n.rf._param_list()) + list(n.model.brdf._weights()) + list(n.model.diffuse_module._head_params())
-                + [n.bg_module.bg_mat, n.bg_module.mipbias])
+    def _grad_params(self, a):
+        """every parameter the pass leaves a gradient in"""
+        return [prm for part in self._grad_table(a) for prm, _ in part]
 
     # ---- accumulators -> parameter gradients ----------------------------------------------------------------------------
     @torch.no_grad()
@@ -757,46 +779,31 @@ class TrainPass:
         """accumulators -> [(parameter, gradient tensor)]: the density gradients unpacked from the packed value + derivative layout
         (with the density_L1 term of scale `l1_scale`, a 0-d device tensor or None, added in the same launch), views of the flat
         buffer for everything else, the env-map table backward (joined if it was queued on its side stream)"""
-        nerf = self.nerf
-        rf, model, bgm = nerf.rf, nerf.model, nerf.bg_module
-        early_env = self._early_env
-        self._early_env = None
-        if early_env is not None and early_env[0] != "done":       # queued by a StepCore on its side stream: its main stream waits for it,
-            early_env[0].join_early_env()
+        rf, bgm = self.nerf.rf, self.nerf.bg_module
+        self._env_join(a)                                           # queued by a StepCore on its side stream: its main stream waits for it,
         self.join_contexts()                                        # ... and this stream for every chunk context's main stream
         p = rf._tables()[0]
         l1 = None
         if l1_scale is not None:          # the L1 term's gradient rides in the unpack launch (one launch less on the step's tail)
             l1 = ([x.detach() for x in list(rf.density_rf.app_plane) + list(rf.density_rf.app_line)], l1_scale)
         hip.vm_unpack_density_grad(p, a.g_dpk, a.g_dlk, out=(a.gp, a.gl), l1=l1)
-        gp, gl = a.gp, a.gl
-        if a.pairs is None:       # (parameter, gradient tensor) of everything that lives in the persistent buffers
-            pairs = list(zip(rf._param_list(), rf._grads_to_param_layout(gp, gl, a.g_apl, a.g_ali, a.g_basis)))
-            m = model.brdf.mlp
-            pairs += list(zip((m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias), a.g_mlp))
-            hps = model.diffuse_module._head_params()
-            for i, (lo, hi) in enumerate(((0, 3), (3, 6), (6, 9), (9, 11))):
-                pairs += [(hps[2 * i], a.g_hW[lo:hi]), (hps[2 * i + 1], a.g_hb[lo:hi])]
-            a.pairs = [(prm, g) for prm, g in pairs if prm.requires_grad]
-        grads = list(a.pairs)
+        self._grad_table(a)
+        grads = list(a.pairs)             # (parameter, gradient tensor) of everything that lives in the persistent buffers as .grad reads it
         if a.used_env:
-            act, sat, pole = bgm._tables()
-            sc = bgm._dev_scalars()
-            if early_env is not None:
-                d_bg = early_env[1]
-            else:
-                d_bg = a.d_bg = hip.sat_build_bwd(a.d_sat.clone() if keep_sat else a.d_sat, bgm.bg_mat.detach(), act, a.d_pole, sc=sc,
-                                                  out=a.d_bg)
+            if a.env_bwd == ENV_NOT_RUN:  # no core queued it, no collective has summed it: here
+                self._env_run(a, keep_sat)
+            d_bg = a.d_bg
             if bgm.bg_mat.requires_grad:
-                if a.d_bg_view is None or a.d_bg_view[0] is not d_bg:
-                    a.d_bg_view = (d_bg, d_bg.reshape(bgm.bg_mat.shape))
-                grads.append((bgm.bg_mat, a.d_bg_view[1]))
+                if a.d_bg_view is None:
+                    a.d_bg_view = d_bg.reshape(bgm.bg_mat.shape)
+                grads.append((bgm.bg_mat, a.d_bg_view))
             if bgm.brightness_lr != 0 or bgm.mul_lr != 0:           # lr 0 (microfacet_tensorf2.yaml:150-151): no update anyway
-                d_pre = d_bg / sc[2]
+                d_pre = d_bg / bgm._dev_scalars()[2]
                 grads.append((bgm.brightness, d_pre.sum(dtype=torch.float64)))
                 grads.append((bgm.mul, (d_pre * bgm.bg_mat.detach().reshape(d_pre.shape)).sum(dtype=torch.float64)))
             if bgm.mipbias.requires_grad:
                 grads.append((bgm.mipbias, a.d_mip.to(torch.float64).reshape(())))
+        a.env_bwd = ENV_NOT_RUN           # (consumed: a sum that goes on -- the autograd node -- runs it again over the longer sum)
         return [(prm, g) for prm, g in grads if prm.requires_grad]
 
     @torch.no_grad()
@@ -831,9 +838,9 @@ class TrainPass:
         """a gradient a chunk left in .grad OUTSIDE the accumulators (a chunk that went through the operator graph) on a rank whose
         fused chunks produced none: moved into the accumulator tensor, which is what the ranks sum"""
         a = self._acc_cache
-        self.assign_reduced(False, False)          # (builds the pairs)
-        bgm = self.nerf.bg_module
-        for prm, g in a.pairs + [(bgm.bg_mat, a.d_bg)]:
+        bg_mat = self.nerf.bg_module.bg_mat
+        early = self._grad_table(a)[1]
+        for prm, g in a.pairs + [pg for pg in early if pg[0] is bg_mat]:
             if prm.grad is not None and prm.grad.data_ptr() != g.data_ptr():
                 g.add_(prm.grad.reshape(g.shape).to(g.dtype))
                 prm.grad = g.reshape(prm.shape) if g.shape != prm.shape else g
@@ -842,16 +849,7 @@ class TrainPass:
         """a rank that had no gradient of its own (no chunk with a sample / no env-map lookup) takes the ranks' sums: .grad of the
         field + shading parameters (`field`) / of the env map (`env`) from the accumulator tensors the collectives summed into"""
         a = self._acc_cache
-        if a.pairs is None:
-            n = self.nerf
-            rf, model = n.rf, n.model
-            pairs = list(zip(rf._param_list(), rf._grads_to_param_layout(a.gp, a.gl, a.g_apl, a.g_ali, a.g_basis)))
-            m = model.brdf.mlp
-            pairs += list(zip((m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias), a.g_mlp))
-            hps = model.diffuse_module._head_params()
-            for i, (lo, hi) in enumerate(((0, 3), (3, 6), (6, 9), (9, 11))):
-                pairs += [(hps[2 * i], a.g_hW[lo:hi]), (hps[2 * i + 1], a.g_hb[lo:hi])]
-            a.pairs = [(prm, g) for prm, g in pairs if prm.requires_grad]
+        self._grad_table(a)
         if field:
             for prm, g in a.pairs:
                 prm.grad = g
@@ -872,15 +870,6 @@ def _white(dev):
     if k not in _CONST:
         _CONST[k] = torch.ones((1, 3), dtype=torch.float32, device=dev)
     return _CONST[k]
-
-
-def _zeros(like):
-    """a read-only zero tensor of `like`'s shape (a view of one buffer that only grows: no fill per step)"""
-    k = ("zeros", like.device)
-    n = like.numel()
-    if k not in _CONST or _CONST[k].numel() < n:
-        _CONST[k] = torch.zeros(max(n, 1 << 16) * 5 // 4, dtype=torch.float32, device=like.device)
-    return _CONST[k][:n].view(like.shape)
 
 
 def _one(dev):

@@ -144,34 +144,30 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
                               "the pass: non-default arguments, a chunk without bounce rows, or a second pending "
                               "forward); `nerf.operator_graph_forwards` counts these calls", RuntimeWarning, stacklevel=3)
         if recur == 0:          # one gradient pass: primary and re-traced rays share the table-gradient nodes
-            passes = [m for m in (self.rf, self.bg_module, getattr(self.model, "brdf", None),
-                                  getattr(self.model, "diffuse_module", None)) if hasattr(m, "begin_pass")]
-            for m in passes:
-                m.begin_pass()
-            nz = noise if noise is not None else self._noise
-            if nz is not None and hasattr(nz, "begin_pass"):
-                nz.begin_pass()                         # the pass's uniform / normal pools, one generator launch each
-            # derived tables of the field (packed density planes) depend only on the parameters: queue their rebuild now, so
-            # that it is issued while the GPU may still be busy with the previous step and before the sampler's read-back
-            if rays.is_cuda:
-                self.rf._fwd_tables() if hasattr(self.rf, "_fwd_tables") else self.rf._tables()
-                if hasattr(self.bg_module, "_tables"):          # summed-area table + SH projection of the environment
-                    self.bg_module._tables()
-                    if hasattr(self.model, "brdf"):             # the microfacet model's diffuse irradiance (G=100)
-                        self.bg_module.get_spherical_harmonics(100)
-                if is_train and torch.is_grad_enabled():            # pass tokens / stacked weights of the shading modules
-                    for m, fn in ((getattr(self.model, "diffuse_module", None), "head_pass"),
-                                  (getattr(self.model, "brdf", None), "mlp_pass")):
-                        if m is not None and hasattr(m, fn) and getattr(m, "fused", True):
-                            getattr(m, fn)()
-                    self.rf._pass_token()
-            try:
+            from ..fast_step import module_pass
+
+            def render_pass():
+                nz = noise if noise is not None else self._noise
+                if nz is not None and hasattr(nz, "begin_pass"):
+                    nz.begin_pass()                         # the pass's uniform / normal pools, one generator launch each
+                # derived tables of the field (packed density planes) depend only on the parameters: queue their rebuild now, so
+                # that it is issued while the GPU may still be busy with the previous step and before the sampler's read-back
+                if rays.is_cuda:
+                    self.rf._fwd_tables() if hasattr(self.rf, "_fwd_tables") else self.rf._tables()
+                    if hasattr(self.bg_module, "_tables"):          # summed-area table + SH projection of the environment
+                        self.bg_module._tables()
+                        if hasattr(self.model, "brdf"):             # the microfacet model's diffuse irradiance (G=100)
+                            self.bg_module.get_spherical_harmonics(100)
+                    if is_train and torch.is_grad_enabled():            # pass tokens / stacked weights of the shading modules
+                        for m, fn in ((getattr(self.model, "diffuse_module", None), "head_pass"),
+                                      (getattr(self.model, "brdf", None), "mlp_pass")):
+                            if m is not None and hasattr(m, fn) and getattr(m, "fused", True):
+                                getattr(m, fn)()
+                        self.rf._pass_token()
                 return self._render(rays, focal, start_mipval, bg_col, stepmul, recur, override_near, output_alpha,
                                     dynamic_batch_size, gt_normals, override_alpha_thres, is_train, ndc_ray, N_samples,
                                     tonemap, draw_debug, max_weight_N, noise)
-            finally:
-                for m in passes:
-                    m.end_pass()
+            return module_pass(self, render_pass)
         return self._render(rays, focal, start_mipval, bg_col, stepmul, recur, override_near, output_alpha,
                             dynamic_batch_size, gt_normals, override_alpha_thres, is_train, ndc_ray, N_samples, tonemap,
                             draw_debug, max_weight_N, noise)
@@ -192,11 +188,9 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
             if self._noise is None:
                 self._noise = DeviceNoise(dev, seed=20211200)
             noise = self._noise
-        c = tp.core()
-        bg = bg_col.detach().to(device=dev, dtype=torch.float32).reshape(1, 3)
-        c.white = bg                                # (the background colour of the primary rays; the Trainer passes white)
+        bg = bg_col.detach().to(device=dev, dtype=torch.float32).reshape(1, 3)     # (of the primary rays; the Trainer passes white)
         try:
-            res = tp.forward_autograd(rays if rays.is_contiguous() else rays.contiguous(), focal, noise)
+            res = tp.forward_autograd(rays if rays.is_contiguous() else rays.contiguous(), focal, noise, bg)
         except Unsupported:
             return None
         if res is None:                             # no sample kept (train.py:567-568 skips the chunk): background only, the module

@@ -743,9 +743,7 @@ class Trainer:
         self.reduce.begin_step()
         early = None
         if fast is not None and self.reduce.active() and rays is not None and rays.is_cuda:
-            comm = fast._side.get("comm")
-            if comm is None:
-                comm = fast._side["comm"] = torch.cuda.Stream()
+            comm = fast.comm_stream()
             dev_ = rays.device
             def start_early(behind_chunks=False):
                 nonlocal tv_env_done

@@ -1362,3 +1362,86 @@ def _tape_free_vs_autograd(phase):
             rel = float((a.double() - f.double()).norm() / a.double().norm().clip(min=1e-30))
             assert rel <= 2e-5, (other, k, rel)
         assert set(gf[0]) <= set(ga[0])
+
+
+def _small_fused_model():
+    """the smallest model of this file (the e2e_small fixtures: 48^3 grid, 32 x 64 environment map) with the fused passes on, and the
+    first 64 of the fixture's rays"""
+    g = Golden("e2e_small_train")
+    nerf, _ = _build(g)
+    nerf.fused_training_pass = True
+    nerf.sampler.update(nerf.rf, init=False)
+    nerf.sampler.update(nerf.rf, init=True)
+    return nerf, g["rays"][:64].to(DEV).contiguous(), g["focal"]
+
+
+def test_only_unsupported_leaves_the_fused_pass_for_the_operator_graph():
+    """The fused pass hands a chunk to the module / operator-graph path on `fast_step.Unsupported` and on nothing else.  An error
+    whose TEXT says "Unsupported" -- here a noise source whose begin_pass (called from inside the C++ pass) raises a RuntimeError --
+    reaches the caller of render_chunk and of Trainer.step as that RuntimeError, and no forward was re-run through the operator
+    graph.  A chunk that IS outside the pass still raises Unsupported: no sample kept (rays that miss the volume), where the
+    renderer and the training forward still fall back to the module, and no bounce row (thrown by the C++ pass itself)."""
+    from nmf_amd.config import resolved_config
+    from nmf_amd.fast_step import Unsupported
+    from nmf_amd.noise import DeviceNoise
+    from nmf_amd.renderer import _eval_pass, render_images
+    from nmf_amd.trainer import Trainer
+
+    class FailingNoise(DeviceNoise):
+        def begin_pass(self):
+            raise RuntimeError("Unsupported by this test")
+
+    nerf, rays, focal = _small_fused_model()
+    fp = _eval_pass(nerf)
+    with pytest.raises(RuntimeError, match="Unsupported by this test") as e:
+        fp.render_chunk(rays, focal, FailingNoise(DEV, 1))
+    assert type(e.value) is RuntimeError
+    tr = Trainer(nerf, resolved_config()["params"])
+    assert tr.fast is not None and tr.fast.supported()
+    gt = torch.rand(64, 3, generator=torch.Generator().manual_seed(5)).to(DEV)
+    with pytest.raises(RuntimeError, match="Unsupported by this test") as e:
+        tr.step(rays, gt, focal, noise=FailingNoise(DEV, 1), update_controllers=False, fixed_chunk=64)
+    assert type(e.value) is RuntimeError
+    assert nerf.operator_graph_forwards == 0
+    # ---- no sample: raised by render_chunk itself; the renderer and the training forward fall back to the module
+    o = torch.tensor([[4.0, 4.0, 4.0]]).expand(37, 3)
+    d = torch.nn.functional.normalize(torch.tensor([[1.0, 0.2, 0.1]]), dim=-1).expand(37, 3)      # pointing away
+    away = torch.cat([o, d], -1).to(DEV).contiguous()
+    with pytest.raises(Unsupported, match="no sample"):
+        fp.render_chunk(away, focal, DeviceNoise(DEV, 1))
+    ims = render_images(nerf, away, focal, 64, DeviceNoise(DEV, 1), keys=("rgb_map", "acc_map"))
+    assert_close(ims["rgb_map"].cpu(), torch.ones(37, 3), what="background only")
+    ims, st = nerf(away, focal, bg_col=torch.ones(3), is_train=True, ndc_ray=False, noise=DeviceNoise(DEV, 1))
+    assert st["n_samples"] == [0] and nerf.operator_graph_forwards == 1
+    # ---- no bounce row: thrown by the C++ pass as its own exception type, seen here as Unsupported
+    nerf, rays, focal = _small_fused_model()
+    nerf.model.test_rays_per_ray = 0.0              # counts = floor(w * 0 + U - 0.5) <= 0: no sample spawns a secondary ray
+    with pytest.raises(Unsupported, match="no bounce rows"):
+        _eval_pass(nerf).render_chunk(rays, focal, DeviceNoise(DEV, 1))
+
+
+def test_first_fused_training_forward_honours_the_background_colour():
+    """The background colour of the primary rays is an argument of the fused training forward: the FIRST fused forward of a freshly
+    built model with bg_col = (0.2, 0.5, 0.8) equals the operator-graph forward of the same model under the same replayed noise
+    (rgb_map to the 1e-4 of this file's small fixtures), and it is not the white-background image: on a ray with acc < 0.99 the
+    background contributes (1 - acc) * colour, 10 x the comparison's tolerance apart at the least."""
+    from nmf_amd.noise import ReplayNoise
+    nerf, rays, focal = _small_fused_model()
+
+    def forward(fused, col):
+        nerf.fused_training_pass = fused
+        torch.manual_seed(11)
+        ims, _ = nerf(rays, focal, bg_col=col, is_train=True, ndc_ray=False, noise=ReplayNoise(DEV, None))
+        return ims["rgb_map"].detach().cpu(), ims["acc_map"].detach().cpu()
+
+    col = torch.tensor([0.2, 0.5, 0.8])
+    got, acc = forward(True, col)                   # the first fused forward of this model
+    assert nerf.operator_graph_forwards == 0
+    ref, acc_ref = forward(False, col)
+    assert nerf.operator_graph_forwards == 1
+    assert_close(acc, acc_ref, rtol=1e-5, atol=1e-6, what="acc_map")
+    assert_close(got, ref, rtol=1e-4, atol=1e-4, what="rgb_map, bg_col = (0.2, 0.5, 0.8)")
+    white, _ = forward(True, torch.ones(3))
+    apart = (got - white).abs().max(dim=1).values
+    print("rays with acc < 0.99:", int((acc < 0.99).sum()), "largest difference to the white image:", float(apart.max()))
+    assert bool(((apart > 1e-3) & (acc < 0.99)).any())
