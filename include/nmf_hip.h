@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 121
+#define NMF_ABI_VERSION 122
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -805,6 +805,30 @@ int nmf_tv_fwd_bwd(const float* const x[], float* const g[], const int32_t* shap
 int nmf_env_resample(const float* src, int32_t kind, int32_t Hs, int32_t Ws, float r00, float r01, float r02, float r10, float r11,
                      float r12, float r20, float r21, float r22, float gain, int32_t supersample, float* dst, int32_t H, int32_t W,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Relighting evaluation: the pixel arithmetic of scripts/relighting_calc.ipynb and of the HDR frame renderer.py:425-429 stores
+ * (nmf_amd/relight_eval.py).  Images are n_img x H x W pixels, P = H W.  srgb / srgb_inverse are
+ * modules/tonemap.py:38-55 (forward limit 0.0031308 with max(x, limit) under the power, inverse limit 0.04045).
+ *
+ * nmf_relight_frame: rgb_lin [n_img][P][3] (the composited radiance sum_k w_k c_k of nmf_ray_compose_fwd), acc [n_img][P] ->
+ *   out [n_img][P][3] = srgb_inverse(srgb_noclip(rgb_lin) + (1 - acc)).
+ * nmf_relight_ratio: pred [n_img][P][3], gt [n_img][P][4] (RGBA, 16-byte aligned) -> sum [n_img][3] (double), the sum of
+ *   gt_c / max(pred_c, 1e-7) (an fp32 quotient, added in double) over the pixels with gt_a > 0.5 and min_c pred_c > 0.01 (both
+ *   strict), and count [n_img] (int64), the number of those pixels.
+ * nmf_relight_adjust: tp [n_img][P][3] = clip(srgb((pred_c * multi_c) * gt_a + (1 - gt_a)), 0, 1), tg [n_img][P][3] =
+ *   clip(srgb(gt_c + (1 - gt_a)), 0, 1), sqerr [n_img] (double) = sum over pixels and channels of the fp32 (tp - tg)^2.
+ * workspace (16-byte aligned) >= the matching *_workspace_bytes(n_img, H, W) (0 for sizes the call refuses); its content before the
+ * call does not matter.  No atomics: per-workgroup partials added in workgroup order, the same bytes on every run.  Refused (nothing
+ * launched): a null pointer, n_img, H or W below 1, a misaligned gt / workspace, a workspace that is too small, a multiplier that is
+ * not finite (NMF_EINVAL); more pixels than one call's grid covers (NMF_ERANGE). */
+int nmf_relight_frame(const float* rgb_lin, const float* acc, int64_t n_img, int64_t H, int64_t W, float* out, void* stream);
+int64_t nmf_relight_ratio_workspace_bytes(int64_t n_img, int64_t H, int64_t W);
+int nmf_relight_ratio(const float* pred, const float* gt, int64_t n_img, int64_t H, int64_t W, double* sum, int64_t* count,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int64_t nmf_relight_adjust_workspace_bytes(int64_t n_img, int64_t H, int64_t W);
+int nmf_relight_adjust(const float* pred, const float* gt, float multi_r, float multi_g, float multi_b, int64_t n_img, int64_t H,
+                       int64_t W, float* tp, float* tg, double* sqerr, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1337,7 +1337,7 @@ PYBIND11_MODULE(_nmf_host, m) {
         .def("train_backward", &StepCore::train_backward)
         .def("has_pending", &StepCore::has_pending)
         .def("render", &StepCore::render, py::arg("rays"), py::arg("focal"), py::arg("noise"), py::arg("want_maps"),
-             py::arg("want_materials") = false)
+             py::arg("want_materials") = false, py::arg("want_linear") = false)
         .def("begin_step", &StepCore::begin_step)
         .def("join_env_table_backward", &StepCore::join_env_table_backward)
         .def("env_was_used", &StepCore::env_was_used)

@@ -242,8 +242,11 @@ class StepCore {
     // want_materials: also the material maps of level 0 (renderer.py:440-463) as one [B,15] block (nmf_material_maps: albedo |
     // roughness | diffuse | tint | spec).  Queued after the whole level tree: the appearance query over all kept
     // samples, then one launch; no noise is drawn and no launch the other outputs come from changes.
-    // -> dict(rgb_map, acc, kept, n_samples, [depth, world_normal], [materials]), or None when the sampler kept no sample
-    py::object render(const Tensor& rays, double focal, py::object noise, bool want_maps, bool want_materials = false) {
+    // want_linear: also rgb_lin [B,3], the composited radiance sum_k w_k c_k before tonemap, clip and background: the buffer
+    // nmf_ray_compose_fwd writes next to acc (nothing is launched or allocated for it)
+    // -> dict(rgb_map, acc, kept, n_samples, [depth, world_normal], [materials], [rgb_lin]), or None when the sampler kept no sample
+    py::object render(const Tensor& rays, double focal, py::object noise, bool want_maps, bool want_materials = false,
+                      bool want_linear = false) {
         begin(noise);
         eval_z_ = want_maps;
         std::unique_ptr<CoreLevel> t;
@@ -261,6 +264,7 @@ class StepCore {
         out["kept"] = t->B;
         out["n_samples"] = t->n_samples;
         if (want_materials) out["materials"] = material_maps_(*t);
+        if (want_linear) out["rgb_lin"] = t->rgb_lin;
         if (want_maps) {
             if (!t->S.z.has_value() || !t->nr.has_value()) throw UnsupportedChunk("evaluation maps need the sampler's z values and dense normals");
             out["depth"] = segment_sum(t->S.z->view({t->M, 1}), OT(t->w), t->offsets, t->B, 1, main_stream).view({t->B});

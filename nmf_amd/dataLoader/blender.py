@@ -7,7 +7,12 @@ frames; produces the tensors train.py / renderer.py consume:
 
 Pixel centres at +0.5, camera looks down +z after the blender->opencv flip (:45-47), directions unit-normalised (:120-122),
 fx = 0.5 w / tan(camera_angle_x / 2) (:97-104).  Ground-truth normal maps `{file_path}_normal{normal_ext}` are read per view
-for evaluation (get_normal, :236-247); training on them (stack_norms), EXR frames and depth are outside the microfacet_tensorf2 path.
+for evaluation (get_normal, :236-247); training on them (stack_norms) and depth are outside the microfacet_tensorf2 path.
+
+EXR frames (`"ext": ".exr"` in the transforms file, or any frame path containing `exr`; the `relighting/<scene>_exr` sets) are read by
+nmf_amd/exr.py as linear RGBA, HALF or FLOAT, in the reference's order (:159-188): alpha to acc_maps, a testing split blended onto
+white, then the colour through SRGBTonemap with its clip to [0, 1], and `hdr = True`.  get_linear(idx) reads a frame again as stored
+(no blend, no tonemap: the ground truth of the relighting evaluation).  They cannot be resampled: downsample != 1 is refused.
 """
 import json
 import os
@@ -48,6 +53,14 @@ def _read_image(path, wh=None):
     return torch.from_numpy(np.ascontiguousarray(a)).float()   # [h, w, c]
 
 
+def _read_exr(path, downsample=1.0):
+    """a linear OpenEXR frame as stored -> float32 [h, w, c] (its own copy)"""
+    if downsample != 1.0:
+        raise ValueError(f"{path}: EXR frames cannot be downsampled (downsample={downsample}); load them with downsample=1")
+    from nmf_amd import exr
+    return torch.from_numpy(np.array(exr.imread(path), dtype=np.float32))
+
+
 class BlenderDataset(torch.utils.data.Dataset):
     def __init__(self, datadir, stack_norms=False, split="train", downsample=1.0, is_stack=False, N_vis=-1, white_bg=True,
                  is_testing=False):
@@ -67,8 +80,6 @@ class BlenderDataset(torch.utils.data.Dataset):
         with open(os.path.join(self.root_dir, f"transforms_{self.split}.json")) as f:
             meta = self.meta = json.load(f)
         ext = meta.get("ext", ".png")
-        if "exr" in ext:
-            raise NotImplementedError("EXR frames need an OpenEXR reader (not on the microfacet_tensorf2 benchmark path)")
         normal_ext = meta.get("normal_ext", ext)
         self.near_far = meta.get("near_far", [2.0, 6.0])
         self.white_bg = meta.get("white_bg", self.white_bg)
@@ -97,12 +108,23 @@ class BlenderDataset(torch.utils.data.Dataset):
             path = os.path.join(self.root_dir, f"{frame['file_path']}{ext}")
             self.image_paths.append(path)
             self.normal_paths.append(os.path.join(self.root_dir, f"{frame['file_path']}_normal{normal_ext}"))
-            img = _read_image(path, self.img_wh if self.downsample != 1.0 else None)          # [h, w, c]
+            is_exr = "exr" in f"{frame['file_path']}{ext}"                                    # (:182; the frame's own path)
+            if is_exr:
+                img = _read_exr(path, self.downsample)
+            else:
+                img = _read_image(path, self.img_wh if self.downsample != 1.0 else None)      # [h, w, c]
             if img.shape[-1] == 4:
                 self.acc_maps.append(img[..., -1])
             img = img.reshape(-1, img.shape[-1])
+            if is_exr:
+                img = img.double()            # blend and tonemap in float64, rounded once (fp32 steps drift by several ulp in the dark)
             if img.shape[1] == 4 and self.is_testing:
                 img[:, :3] = img[:, :3] * img[:, -1:] + (1 - img[:, -1:])                      # blend A onto white (:165-169)
+            if is_exr:                                                                         # :182-184, after the blend
+                from nmf_amd.modules.tonemap import SRGBTonemap
+                img[:, :3] = SRGBTonemap()(img[:, :3])
+                img = img.float()
+                self.hdr = True
             rays_o, rays_d = get_rays(self.directions, c2w)
             self.all_rays.append(torch.cat([rays_o, rays_d], 1))
             self.all_rgbs.append(img)
@@ -133,6 +155,12 @@ class BlenderDataset(torch.utils.data.Dataset):
         else:
             norms = (norms - 0.5) * 2
         return norms
+
+    def get_linear(self, idx):
+        """view `idx` of an EXR scene as stored: linear RGBA [h, w, 4] float32, no blend and no tonemap; read from the file again"""
+        if not self.hdr:
+            raise ValueError("get_linear: the frames of this scene are not EXR files")
+        return _read_exr(self.image_paths[idx])
 
     def __len__(self):
         return len(self.all_rgbs)

@@ -503,15 +503,16 @@ class TrainPass:
 
     # ---- evaluation: forward only ---------------------------------------------------------------------------------------
     @torch.no_grad()
-    def render_chunk(self, rays, focal, noise, want_maps=False, want_materials=False):
+    def render_chunk(self, rays, focal, noise, want_maps=False, want_materials=False, want_linear=False):
         """`TensorNeRF.forward(rays, focal, bg_col=white, is_train=False, draw_debug=False)` as one C++ call:
         -> (rgb_map [b,3], acc_map [b], b = rays the sampler kept, n_samples) + (depth [b], world_normal [b,3]) with want_maps (the two
         maps of the reference's evaluation branch that need no dense appearance pass, modules/tensor_nerf.py:480-501) + a dict
         {albedo, roughness, diffuse, tint, spec} of [b,3] maps with want_materials (level 0, renderer.py:440-463: one appearance query
-        over the kept samples and nmf_material_maps, queued after everything else; the other outputs keep their bits).  Raises
+        over the kept samples and nmf_material_maps, queued after everything else; the other outputs keep their bits) + rgb_lin [b,3] with
+        want_linear (last: the composited radiance before tonemap, clip and background, the buffer the compose kernel fills).  Raises
         Unsupported (configuration, no sample, no bounce row): the caller renders that chunk through the module."""
-        out = self._pass(lambda core: core.render(rays, float(focal), noise, bool(want_maps), bool(want_materials)),
-                         rays.device, focal, False, _white(rays.device))
+        out = self._pass(lambda core: core.render(rays, float(focal), noise, bool(want_maps), bool(want_materials),
+                                                  bool(want_linear)), rays.device, focal, False, _white(rays.device))
         if out is None:
             raise Unsupported("no sample")
         res = (out["rgb_map"], out["acc"], out["kept"], list(out["n_samples"]))
@@ -520,6 +521,8 @@ class TrainPass:
         if want_materials:
             block = out["materials"]
             res += ({k: block[:, 3 * i:3 * i + 3] for i, k in enumerate(hip.MATERIAL_MAPS)},)
+        if want_linear:
+            res += (out["rgb_lin"],)
         return res
 
     # ---- one chunk: forward, loss, backward (nmf_amd.trainer.Trainer) ------------------------------------------------------

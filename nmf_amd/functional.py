@@ -504,11 +504,12 @@ class BouncePrep(torch.autograd.Function):
 class RayCompose(torch.autograd.Function):
     """weights x row radiance -> pixels in one pass per ray: acc / rgb sums (modules/tensor_nerf.py:448-452), the
     orientation-loss term (:583-587), tonemap (modules/tonemap.py:34-55) and background blend (:658-659).
-    Returns (rgb_map [B,3], acc [B], ori [B] or None)."""
+    Returns (rgb_map [B,3], acc [B], ori [B] or None).  lin_out: a list that receives rgb_lin [B,3], the composited radiance
+    before tonemap, clip and background (the evaluation's "rgb_lin" image; no gradient flows through it)."""
 
     @staticmethod
     def forward(ctx, weight, refl_rows, normals, bg, inv, offsets, ray_id, rays, B, bg_per_ray, tonemap, noclip,
-                want_ori):
+                want_ori, lin_out=None):
         weight = weight.contiguous()
         refl = refl_rows.contiguous() if refl_rows is not None else None
         normals = normals.contiguous() if normals is not None else None
@@ -519,6 +520,8 @@ class RayCompose(torch.autograd.Function):
         ctx.save_for_backward(weight, refl, normals, bg, inv, ray_id, rays, rgb_lin, acc)
         ctx.cfg = (bg_per_ray, tonemap, noclip, want_ori)
         ctx.set_materialize_grads(False)
+        if lin_out is not None:
+            lin_out.append(rgb_lin)
         return rgb_map, acc, ori
 
     @staticmethod
@@ -537,7 +540,7 @@ class RayCompose(torch.autograd.Function):
             d_bg = (1 - acc)[:, None] * d_rgb
             if not bg_per_ray:
                 d_bg = d_bg.sum(0).reshape(bg.shape)
-        return (d_weight, d_refl if ctx.needs_input_grad[1] else None, d_normals, d_bg) + (None,) * 9
+        return (d_weight, d_refl if ctx.needs_input_grad[1] else None, d_normals, d_bg) + (None,) * 10
 
 
 class ShadeCompose(torch.autograd.Function):
@@ -547,7 +550,7 @@ class ShadeCompose(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, normals, bg, inv, offsets, ray_id, rays, B, bg_per_ray, tonemap, noclip, want_ori,
-                V, f0, diff, cnt, row_of_ray, row_off, L, inc, brdf):
+                V, f0, diff, cnt, row_of_ray, row_off, L, inc, brdf, lin_out=None):
         V, f0, diff = V.contiguous(), f0.contiguous(), diff.contiguous()
         L, inc, brdf = L.contiguous(), inc.contiguous(), brdf.contiguous()
         contrib = hip.shade_mix_fwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf)
@@ -562,6 +565,8 @@ class ShadeCompose(torch.autograd.Function):
         ctx.cfg = (bg_per_ray, tonemap, noclip, want_ori)
         ctx.mark_non_differentiable(refl)
         ctx.set_materialize_grads(False)
+        if lin_out is not None:                 # as in RayCompose
+            lin_out.append(rgb_lin)
         return rgb_map, acc, ori, refl
 
     @staticmethod
@@ -590,7 +595,7 @@ class ShadeCompose(torch.autograd.Function):
             d_inc, d_brdf, dL, d_fd = hip.shade_mix_bwd(V, f0, diff, cnt, row_of_ray, L, inc, brdf, d_refl)
         rows = hip.segment_sum_wide(d_fd, 6, row_off, V.shape[0])
         return (d_weight, d_normals, d_bg) + (None,) * 9 + (dV_rows, rows[:, 0:3], rows[:, 3:6], None, None, None, dL, d_inc,
-                                                               d_brdf)
+                                                               d_brdf, None)
 
 
 class BounceRays(torch.autograd.Function):

@@ -98,6 +98,8 @@ EXPORTS = [
     "nmf_mc_count", "nmf_mc_emit", "nmf_mc_workspace_bytes", "nmf_mc_case_triangles",
     "nmf_tv_fwd_bwd", "nmf_tv_workspace_bytes",
     "nmf_env_resample",
+    "nmf_relight_frame", "nmf_relight_ratio", "nmf_relight_ratio_workspace_bytes", "nmf_relight_adjust",
+    "nmf_relight_adjust_workspace_bytes",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -967,6 +969,58 @@ def normal_err(pred, gt, acc, return_map=False):
     _check(_lib.nmf_normal_err(_p(P, torch.float32), _p(G, torch.float32), _p(Acc, torch.float32), C.c_int64(n),
                                C.c_int64(n_px), _p(out), _p(emap), _p(ws), C.c_int64(ws.numel()), _stream()), "nmf_normal_err")
     return (out, emap.reshape(acc.shape)) if return_map else out
+
+
+# ---- relighting evaluation (scripts/relighting_calc.ipynb, renderer.py:425-429; csrc/relight_eval.hip) ---------------------------
+def _relight_images(what, pred, gt=None):
+    """pred [H,W,3] or [n,H,W,3] (and gt of the same pixels with 4 channels), fp32 device tensors -> (pred, gt) contiguous, n, H, W"""
+    if pred.dim() not in (3, 4) or pred.shape[-1] != 3 or (gt is not None and (gt.shape[:-1] != pred.shape[:-1] or gt.shape[-1] != 4)):
+        raise NmfHipError(f"{what}: pred is [H,W,3] or [n,H,W,3] and gt its RGBA counterpart, got {tuple(pred.shape)}"
+                          + (f" / {tuple(gt.shape)}" if gt is not None else ""))
+    for t in (pred, gt):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise NmfHipError(f"{what}: fp32 device tensors (no CPU path), got {t.dtype} on {t.device}")
+    P, G = _batched(pred, 3), (_batched(gt, 3) if gt is not None else None)
+    return P, G, P.shape[0], P.shape[1], P.shape[2]
+
+
+def relight_frame(rgb_lin, acc):
+    """nmf_relight_frame: the linear HDR frame the reference stores (renderer.py:425-429) from the composited radiance rgb_lin [..., 3]
+    and the opacity acc [...]: srgb_inverse(srgb_noclip(rgb_lin) + (1 - acc)), in rgb_lin's shape"""
+    if rgb_lin.dim() < 2 or rgb_lin.shape[-1] != 3 or acc.shape != rgb_lin.shape[:-1]:
+        raise NmfHipError(f"relight_frame: rgb_lin [..., 3] and acc [...], got {tuple(rgb_lin.shape)} / {tuple(acc.shape)}")
+    L, A = rgb_lin.contiguous(), acc.contiguous()
+    ptr = _p(L, torch.float32), _p(A, torch.float32)
+    out = torch.empty_like(L)
+    n, h, w = (L.shape[0], L.shape[1], L.shape[2]) if L.dim() == 4 else (1, 1, A.numel())
+    _check(_lib.nmf_relight_frame(*ptr, n, h, w, _p(out), _stream()), "nmf_relight_frame")
+    return out
+
+
+def relight_ratio(pred, gt):
+    """nmf_relight_ratio (relighting_calc.ipynb cell lines 232-233): pred [n,H,W,3], gt [n,H,W,4] (or one image) -> (float64 [n,3] sums
+    of gt_c / max(pred_c, 1e-7) over the pixels with gt_a > 0.5 and min_c pred_c > 0.01, int64 [n] counts of those pixels)"""
+    P, G, n, H, W = _relight_images("relight_ratio", pred, gt)
+    sums = torch.empty((n, 3), dtype=torch.float64, device=P.device)
+    count = torch.empty(n, dtype=torch.int64, device=P.device)
+    ws = torch.empty(max(int(_lib.nmf_relight_ratio_workspace_bytes(n, H, W)), 16), dtype=torch.uint8, device=P.device)
+    _check(_lib.nmf_relight_ratio(_p(P), _p(G), n, H, W, _p(sums), _p(count), _p(ws), ws.numel(), _stream()), "nmf_relight_ratio")
+    return sums, count
+
+
+def relight_adjust(pred, gt, multi):
+    """nmf_relight_adjust (cell lines 243-246): -> (tp, tg fp32 in pred's shape, sqerr float64 [n]): the prediction times the per-channel
+    multiplier blended onto white with gt's alpha, and gt on white, both tonemapped and clipped; sqerr = sum (tp - tg)^2 per image"""
+    P, G, n, H, W = _relight_images("relight_adjust", pred, gt)
+    m = [float(v) for v in np.asarray(multi, dtype=np.float32).reshape(-1)]
+    if len(m) != 3:
+        raise NmfHipError("relight_adjust: multi is one multiplier per channel")
+    tp, tg = torch.empty_like(P), torch.empty_like(P)
+    sqerr = torch.empty(n, dtype=torch.float64, device=P.device)
+    ws = torch.empty(max(int(_lib.nmf_relight_adjust_workspace_bytes(n, H, W)), 16), dtype=torch.uint8, device=P.device)
+    _check(_lib.nmf_relight_adjust(_p(P), _p(G), *m, n, H, W, _p(tp), _p(tg), _p(sqerr), _p(ws), ws.numel(), _stream()),
+           "nmf_relight_adjust")
+    return tp.reshape(pred.shape), tg.reshape(pred.shape), sqerr
 
 
 # ---- material maps of the evaluation pass (renderer.py:440-463) ------------------------------------------------------

@@ -265,18 +265,19 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
             bg = bg_col.to(device=dev, dtype=torch.float32).reshape(1, 3)
 
         want_stats = recur == 0 and (is_train or not draw_debug)
+        lin = [] if (recur == 0 and not is_train) else None     # evaluation: the compose call's rgb_lin is the "rgb_lin" image
         # one pass per ray: acc (:448), rgb (:452), orientation term (:583-587), tonemap (:658), background (:659)
         if shaded is not None and shaded.mix_args is not None and shaded._refl_rows is None:
             # Fresnel mix of the bounce rows + the per-ray sums as one graph node
             rgb_map, acc_map, ori, refl = ShadeCompose.apply(
                 weight, world_normal, bg, shaded.inv, offsets, S.ray_id, S.rays, B, per_ray_bg, bool(tonemap), bool(self.hdr),
-                bool(want_stats and M > 0), *shaded.mix_args)
+                bool(want_stats and M > 0), *shaded.mix_args, *(() if lin is None else (lin,)))
             shaded.refl_rows = refl              # detached: the debug maps of this pass read values only
         else:
             rgb_map, acc_map, ori = RayCompose.apply(
                 weight, shaded.refl_rows if shaded is not None else None, world_normal if M > 0 else None, bg,
                 shaded.inv if shaded is not None else None, offsets, S.ray_id, S.rays, B, per_ray_bg, bool(tonemap),
-                bool(self.hdr), bool(want_stats and M > 0))
+                bool(self.hdr), bool(want_stats and M > 0), *(() if lin is None else (lin,)))
 
         if not is_train and draw_debug:                                                              # :480-566
             with torch.no_grad():
@@ -298,6 +299,8 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
             images = LazyImages(shaded)
         images["rgb_map"] = rgb_map
         images["acc_map"] = acc_map.detach()
+        if lin:
+            images["rgb_lin"] = lin[0]
         return images, stats
 
 

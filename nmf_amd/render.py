@@ -22,6 +22,12 @@ Relighting (nmf_amd/relight.py): --fixed-bg also takes a panoram
 --bg-res without an optimisation run; --env-rotate YAW PITCH ROLL (degrees, +z up) rotates the lighting -- the checkpoint's own map or
 the --fixed-bg one; --light-turntable N then renders view 0 N times under a further yaw of 360 k / N (light_000.png ... in --out) and
 the line gains light_frames and, per frame, the seconds of the environment update and of the render.
+
+    python -m nmf_amd.render --ckpt log/car.th --datadir /data/relighting/car_exr --fixed-bg forest.exr --relight-eval log/car/imgs_test_ori
+
+--relight-eval DIR (nmf_amd/relight_eval.py; the reference's scripts/relighting_calc.ipynb) scores the relit test views
+of an EXR set against its ground truth: HDR frames {idx:03d}.exr, adjusted/{idx:03d}.png and stats.yaml go to DIR, and the line gains
+relight = {psnr, ssim, multiplier, views}.  Combines with --env-rotate, --bg-res and --n-vis.
 """
 import argparse
 import json
@@ -116,11 +122,15 @@ def main(argv=None):
                     help="rotate the lighting (degrees, +z up): the checkpoint's own environment map or the --fixed-bg one")
     ap.add_argument("--light-turntable", type=int, default=0, metavar="N",
                     help="render view 0 N times under a yaw of 360 k / N of the lighting (light_000.png ... in --out)")
+    ap.add_argument("--relight-eval", default=None, metavar="DIR",
+                    help="with --datadir of an EXR test set: fit the brightness multiplier and write HDR frames, adjusted/ and stats.yaml")
     args = ap.parse_args(argv)
     if args.light_turntable < 0:
         ap.error("--light-turntable takes a number of frames")
     if args.eval_dir and not args.datadir:
         ap.error("--eval-dir needs --datadir (ground truth of a Blender scene)")
+    if args.relight_eval and not args.datadir:
+        ap.error("--relight-eval needs --datadir (an EXR test set with ground truth)")
     if args.material_maps and not args.eval_dir:
         ap.error("--material-maps needs --eval-dir")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -129,6 +139,8 @@ def main(argv=None):
     if args.datadir:
         from .dataLoader import BlenderDataset
         ds = BlenderDataset(args.datadir, split="test", is_stack=True, N_vis=args.n_vis)
+        if args.relight_eval and not ds.hdr:
+            ap.error("--relight-eval needs an EXR test set (linear RGBA ground truth); this scene's frames are not EXR files")
         rays, focal, near_far = ds.all_rays.to(dev), float(ds.fx), tuple(ds.near_far)
         gt = ds.all_rgbs.reshape(rays.shape[0], -1, 3).to(dev)
         wh = ds.img_wh
@@ -168,6 +180,10 @@ def main(argv=None):
         rec.update(ssim=rec_all["ssim"], norm_err=rec_all["norm_err"],
                    eval_seconds=dict(total=round(time.perf_counter() - t0, 4), render=round(res["seconds"]["render"], 4),
                                      metrics=round(res["seconds"]["metrics"], 4)))
+    if args.relight_eval:
+        from .relight_eval import relight_evaluation
+        res = relight_evaluation(nerf, ds, args.relight_eval, noise=noise, chunk=chunk)
+        rec["relight"] = dict(psnr=round(res["psnr"], 3), ssim=round(res["ssim"], 5), multiplier=res["multiplier"], views=res["views"])
     print(json.dumps(rec), flush=True)
     return rec
 

@@ -63,15 +63,18 @@ def render_images(nerf, rays, focal, chunk=None, noise=None, keys=("rgb_map",), 
     """evaluation render (renderer.py:119-170 without the random permutation): eval_batch_size rays per chunk, rendered
     to completion, is_train=False.  keys may name the material maps MATERIAL_KEYS (renderer.py:440-463, [N,3] each): the fused
     pass forms them (TrainPass.render_chunk(want_materials=True)); without it the whole call renders through the module with
-    draw_debug=True, and a chunk the fused pass does not support through the module with draw_debug=True."""
+    draw_debug=True, and a chunk the fused pass does not support through the module with draw_debug=True.  "rgb_lin" [N,3] is the
+    composited radiance sum_k w_k c_k before tonemap, clip and background (the relighting evaluation's input): the buffer the compose
+    kernel writes next to acc_map, handed out by the fused pass (want_linear) and by the module alike."""
     chunk = chunk or nerf.eval_batch_size
     kw.setdefault("draw_debug", False)
     module_kw = dict(bg_col=torch.ones(3, device=rays.device), is_train=False, ndc_ray=False, noise=noise, **kw)
     tensorf = nerf
     maps = bool(set(keys) & {"depth", "world_normal"})
     mats = bool(set(keys) & set(MATERIAL_KEYS))
+    lin = "rgb_lin" in keys
     fast = _eval_pass(nerf) if (rays.is_cuda and not kw["draw_debug"]
-                                and set(keys) <= {"rgb_map", "acc_map", "depth", "world_normal", *(MATERIAL_KEYS if mats else ())}
+                                and set(keys) <= {"rgb_map", "acc_map", "depth", "world_normal", "rgb_lin", *(MATERIAL_KEYS if mats else ())}
                                 and len(kw) == 1) else None
     if mats and fast is None:
         module_kw["draw_debug"] = True            # the module's evaluation branch forms the maps (modules/tensor_nerf.py:480-566)
@@ -86,14 +89,17 @@ def render_images(nerf, rays, focal, chunk=None, noise=None, keys=("rgb_map",), 
                         from .noise import DeviceNoise
                         nerf._noise = DeviceNoise(pending.device, seed=20211200)
                     nz = nerf._noise
-                out = fast.render_chunk(pending, focal_, nz, want_maps=maps, **(dict(want_materials=True) if mats else {}))
+                out = fast.render_chunk(pending, focal_, nz, want_maps=maps, **(dict(want_materials=True) if mats else {}),
+                                        **(dict(want_linear=True) if lin else {}))
             except Unsupported:
                 return nerf(pending, focal_, **(dict(module_kw, draw_debug=True) if (maps or mats) else module_kw))
             ims_ = dict(rgb_map=out[0], acc_map=out[1])
             if maps:
                 ims_.update(depth=out[4], world_normal=out[5])
+            if lin:
+                ims_.update(rgb_lin=out[-1])
             if mats:
-                ims_.update(out[-1])
+                ims_.update(out[-2 if lin else -1])
             return ims_, dict(rays_kept=out[2], n_samples=out[3])
     ims, _ = chunk_renderer(rays, tensorf, focal, keys=keys, chunk=chunk, render2completion=True, **module_kw)
     return ims["rgb_map"] if tuple(keys) == ("rgb_map",) else ims
