@@ -639,7 +639,7 @@ extern "C" int nmf_ray_compose_fwd(const float* weight, const float* refl_rows, 
     if (B == 0) return NMF_OK;
     // weight may be NULL when no ray has a sample (every segment empty)
     NMF_REQUIRE(rays && offsets && bg && rgb_map && acc && rgb_lin, NMF_EINVAL, "nmf_ray_compose_fwd: null");
-    NMF_REQUIRE(!ori || normals, NMF_EINVAL, "nmf_ray_compose_fwd: ori needs normals");
+    NMF_REQUIRE(!ori || normals || !weight, NMF_EINVAL, "nmf_ray_compose_fwd: ori needs normals");   // (no sample: no normal is read)
     if (B <= 16384)      // few rays with long segments (primary rays): one wave per ray
         NMF_LAUNCH(k_ray_compose_fwd_wave<64>, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, weight,
                            refl_rows, inv, normals, rays, offsets, B, bg, (int)bg_per_ray, (int)tonemap, (int)noclip,
