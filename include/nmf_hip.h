@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 122
+#define NMF_ABI_VERSION 123
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -60,7 +60,6 @@ int nmf_host_free_mapped(void* host_ptr);
 int nmf_publish_i64x2(const int64_t* src_dev, void* dst_mapped_dev, int64_t seq, void* stream);
 int nmf_wait_seq(const void* host_ptr, int64_t seq, double timeout_s);
 int nmf_stream_wait_event(void* stream, void* event);
-int nmf_memcpy_d2h_async(void* dst_host, const void* src_dev, int64_t nbytes, void* stream);
 /* Launch probe (measurement plumbing: bench.py's per-kernel HIP-event timing on the launching stream): when set, EVERY kernel launch
  * of the library calls probe(kernel_name, stream, 0) in front of and probe(kernel_name, stream, 1) behind the launch, on the calling
  * thread.  kernel_name is the kernel's identifier as rocprofv3 --kernel-trace prints it (without arguments).  NULL removes it. */
@@ -107,17 +106,14 @@ int64_t nmf_alpha_coarse_words(const int32_t grid[3]);
 /* Pass 2: exclusive scan of counts + the sample budget of alphagrid.py:353-364:
  * if max_samples > 0 and sum(counts) > max_samples then whole_valid[i] = cumsum(counts)[i] < max_samples
  * else all rays valid.  totals[0] = M (kept samples of valid rays), totals[1] = b (valid rays; they
- * are always a prefix).  offsets has B+1 entries (entries past b are clamped to M). */
+ * are always a prefix).  offsets has B+1 entries (entries past b are clamped to M).
+ * publish_mapped_dev (nmf_host_alloc_mapped's device pointer, or NULL): the thread that writes totals also PUBLISHES them,
+ * [M, b, publish_seq], into mapped host memory for a host that waits with nmf_wait_seq -- the size read-back of
+ * alphagrid.py:353-364 (`ray_valid.sum() > max_samples`, a host sync) without a launch of its own. */
 int nmf_march_scan(const int32_t* counts, int64_t B, int64_t max_samples, int64_t* offsets,
                    uint8_t* whole_valid, int64_t* totals, void* workspace, int64_t workspace_bytes,
-                   void* stream);
+                   void* publish_mapped_dev, int64_t publish_seq, void* stream);
 int64_t nmf_march_scan_workspace_bytes(int64_t B);
-/* The same scan; the thread that writes totals also PUBLISHES them: [M, b, publish_seq] into mapped host memory
- * (nmf_host_alloc_mapped's device pointer; NULL = nmf_march_scan) for a host that waits with nmf_wait_seq -- the size
- * read-back of alphagrid.py:353-364 (`ray_valid.sum() > max_samples`, a host sync) without a launch of its own. */
-int nmf_march_scan_publish(const int32_t* counts, int64_t B, int64_t max_samples, int64_t* offsets,
-                           uint8_t* whole_valid, int64_t* totals, void* workspace, int64_t workspace_bytes,
-                           void* publish_mapped_dev, int64_t publish_seq, void* stream);
 
 /* Pass 3: emit the compacted samples of the first b rays: xyzt [M][4] (world xyz, t/focal),
  * ray_id [M], step_id [M], z [M], dist [M] (= z[k+1]-z[k] over ALL candidates, 0 for the last,
@@ -150,24 +146,23 @@ int nmf_vm_pack_density(const nmf_vm_params* p, const float* const planes[3],
                         const float* const lines[3], float* const dpk[3], float* const dlk[3],
                         void* stream);
 
-/* Forward query of M world-space samples.  Outputs (any may be NULL):
+/* Forward query of M_cap world-space samples.  Outputs (any may be NULL):
  * sigma_feat [M], sigma [M] (softplus(clamp(f,-15,1e3)+shift)), grad [M][3] (d sigma_feat/d xyz,
  * reference units), normal [M][3] = normalize(-grad), app [M][24], coef [M][72] (plane*line
  * products, saved for the basis_mat gradient).  Density outputs need dpk/dlk, appearance outputs
- * need app_planes/app_lines/basis ([24][72] row-major). */
-int nmf_vm_query_fwd(const nmf_vm_params* p, const float* xyzt, int64_t M,
-                     const float* const dpk[3], const float* const dlk[3],
-                     const float* const app_planes[3], const float* const app_lines[3],
-                     const float* basis, float* sigma_feat, float* sigma, float* grad, float* normal,
-                     float* app, float* coef, void* stream);
-/* bf16-table variant (BASELINE configs[1], train.py:540 `fp16` autocast is the reference's only precision hook): the same
- * query with every factor table stored as bfloat16 (the upper 16 bits of the fp32 pattern) -- half the bytes per tap --
- * and fp32 arithmetic.  The caller keeps fp32 master tables (Adam, backward walk) and refreshes the bf16 copies after each
- * optimizer step (nmf_multi_copy with dst_is_f64 = 2). */
-int nmf_vm_query_fwd_bf16(const nmf_vm_params* p, const float* xyzt, int64_t M, const uint16_t* const dpk[3],
-                          const uint16_t* const dlk[3], const uint16_t* const app_planes[3],
-                          const uint16_t* const app_lines[3], const float* basis, float* sigma_feat, float* sigma,
-                          float* grad, float* normal, float* app, float* coef, void* stream);
+ * need app_planes/app_lines/basis ([24][72] row-major).
+ * tables_bf16 (BASELINE configs[1], train.py:540 `fp16` autocast is the reference's only precision hook): 0 = every factor
+ * table is fp32; != 0 = every table is stored as bfloat16 (the upper 16 bits of the fp32 pattern) -- half the bytes per tap --
+ * with fp32 arithmetic.  The caller keeps fp32 master tables (Adam, backward walk) and refreshes the bf16 copies after each
+ * optimizer step (nmf_multi_copy with dst_is_f64 = 2).
+ * M_live (DEVICE, may be NULL): the live sample count when it is still on the device (e.g. totals[0] of nmf_march_scan): the
+ * launch is sized by the bound M_cap the caller allocated for (sampler.max_samples, samplers/alphagrid.py:353-364), samples at
+ * or beyond *M_live are neither read nor written.  Lets a caller queue the level-0 pipeline behind the scan without waiting
+ * for its sizes.  Only the general query (density with grad or normal) takes it. */
+int nmf_vm_query_fwd(const nmf_vm_params* p, const float* xyzt, int64_t M_cap, const int64_t* M_live,
+                     const void* const dpk[3], const void* const dlk[3], const void* const app_planes[3],
+                     const void* const app_lines[3], int32_t tables_bf16, const float* basis, float* sigma_feat,
+                     float* sigma, float* grad, float* normal, float* app, float* coef, void* stream);
 /* Density VALUE of M samples from the density factors THEMSELVES: planes[i] [G][G][16] (channel-last storage of
  * rf.density_rf.app_plane.i), lines[i] [G][16] -- what fields/tensoRF.py:181-190 + tensor_base.py:85 compute, for the levels
  * of a pass that need no normals (nmf_amd/fast_step.py "sparse normals").  Same taps, same order of the sums as
@@ -183,28 +178,23 @@ int nmf_vm_query_rows(const nmf_vm_params* p, const float* xyzt, int64_t M, cons
                       const void* const dlk[3], int32_t tables_bf16, float* sigma_feat, float* sigma, float* grad,
                       float* normal, void* stream);
 
-/* Backward.  Upstream adjoints (any may be NULL): d_sigma [M] (wrt activated sigma), d_sigma_feat [M]
- * (wrt the raw feature, added to the former's contribution), d_normal [M][3], d_app [M][24].
- * sigma_feat / grad are the saved forward outputs.  Accumulates into g_dpk[i] [G][G][48],
- * g_dlk[i] [G][32], g_app_planes[i] [G][G][24], g_app_lines[i] [G][24], g_basis [24][72] (basis_mat, may be NULL)
- * -- caller zeroes them.
- * Samples are counting-sorted by 8^3-voxel brick and reduced in LDS per brick (see vm.hip). */
-int nmf_vm_query_bwd(const nmf_vm_params* p, const float* xyzt, int64_t M,
-                     const float* const dpk[3], const float* const dlk[3],
-                     const float* const app_planes[3], const float* const app_lines[3],
-                     const float* basis, const float* sigma_feat, const float* grad,
-                     const float* d_sigma, const float* d_sigma_feat, const float* d_normal,
-                     const float* d_app, float* const g_dpk[3], float* const g_dlk[3],
-                     float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                     void* workspace, int64_t workspace_bytes, void* stream);
-/* Scratch the backward needs (brick ids, bin counters, records in brick order); contents are undefined on return.
- * For nmf_vm_query_bwd_segments M is the total over the segments. */
-int64_t nmf_vm_bwd_workspace_bytes(int64_t M, int32_t grid);
-
-/* The same walk over the concatenation of up to NMF_VM_MAX_SEGMENTS sample sets (no copy): one training pass queries the
- * field for the primary and for the re-traced rays (tensor_nerf.py:286-393 at recur 0 and 1); their adjoints all land in
- * the same tables, so walking them together bins once and flushes every brick both sets touch once.  All non-empty
- * segments must provide the same set of adjoints (d_sigma / d_normal / d_app NULL-ness). */
+/* Backward over the concatenation of up to NMF_VM_MAX_SEGMENTS sample sets (no copy): one training pass queries the field for
+ * the primary and for the re-traced rays (tensor_nerf.py:286-393 at recur 0 and 1); their adjoints all land in the same
+ * tables, so walking them together bins once and flushes every brick both sets touch once.
+ * Per set: upstream adjoints (any may be NULL) d_sigma [M] (wrt activated sigma), d_sigma_feat [M] (wrt the raw feature,
+ * added to the former's contribution), d_normal [M][3], d_app [M][24]; sigma_feat / grad are the saved forward outputs.  All
+ * non-empty segments must provide the same set of adjoints (d_sigma / d_normal / d_app NULL-ness).
+ * Accumulates into g_dpk[i] [G][G][48], g_dlk[i] [G][32], g_app_planes[i] [G][G][24], g_app_lines[i] [G][24],
+ * g_basis [24][72] (basis_mat, may be NULL) -- caller zeroes them.
+ * Samples are counting-sorted by 8^3-voxel brick and reduced in LDS per brick (see vm.hip).
+ * workspace: nmf_vm_bwd_workspace_bytes(total M, grid) bytes of scratch (brick ids, records in brick order, and -- without
+ * `clean` -- the bin counters); contents are undefined on return.
+ * clean (may be NULL: the counters are then zeroed by memset launches of this call), for a caller that walks again and again
+ * (a training loop: train.py:497-747 calls backward() every iteration): the counters of the brick sort, the chunk words of its
+ * scan and the scratch copies of the basis_mat gradient live in `clean`, nmf_vm_bwd_clean_bytes(grid) bytes of device memory
+ * (16-byte aligned) that are ZERO on entry -- zeroed once, when allocated -- and zero again when the kernels of the call have
+ * run (each clears what it has consumed).  No memset launch per walk (two for an appearance walk: 3.5 us + a launch gap each on
+ * the serial tail of a step).  One scratch per walk that may be in flight. */
 #define NMF_VM_MAX_SEGMENTS 4
 typedef struct nmf_vm_bwd_segment {
     const float* xyzt;          /* [M][4] */
@@ -221,49 +211,19 @@ int nmf_vm_query_bwd_segments(const nmf_vm_params* p, const nmf_vm_bwd_segment* 
                               const float* const app_planes[3], const float* const app_lines[3],
                               const float* basis, float* const g_dpk[3], float* const g_dlk[3],
                               float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                              void* workspace, int64_t workspace_bytes, void* stream);
-/* The same call for a caller that walks again and again (a training loop: train.py:497-747 calls backward() every iteration):
- * the counters of the brick sort, the chunk words of its scan and the scratch copies of the basis_mat gradient live in `clean`,
- * nmf_vm_bwd_clean_bytes(grid) bytes of device memory (16-byte aligned) that are ZERO on entry -- zeroed once, when allocated --
- * and zero again when the kernels of the call have run (each clears what it has consumed).  No memset launch per walk (two for
- * an appearance walk: 3.5 us + a launch gap each on the serial tail of a step).  One scratch per walk that may be in flight. */
+                              void* clean, int64_t clean_bytes, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t nmf_vm_bwd_workspace_bytes(int64_t M, int32_t grid);
 int64_t nmf_vm_bwd_clean_bytes(int32_t grid);
-int nmf_vm_query_bwd_segments_clean(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs /*HOST array*/, int32_t n_segs,
-                                    const float* const dpk[3], const float* const dlk[3],
-                                    const float* const app_planes[3], const float* const app_lines[3],
-                                    const float* basis, float* const g_dpk[3], float* const g_dlk[3],
-                                    float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                                    void* clean, int64_t clean_bytes, void* workspace, int64_t workspace_bytes, void* stream);
-/* The brick sort of a walk as a PLAN: it depends on the sample positions alone (not on the adjoints), so a training pass
- * builds it when the positions become known -- under its forward, on a side stream -- and the backward only permutes the
- * adjoints (autograd of fields/tensoRF.py:181-205 sees the same sample set twice: forward and backward).
- *   nmf_vm_bin_plan            positions of up to NMF_VM_MAX_SEGMENTS sample sets -> plan (opaque device buffer of
- *                              nmf_vm_bin_plan_bytes(total M, grid) bytes: slots, brick offsets, work items, sorted positions)
- *   nmf_vm_query_bwd_planned   nmf_vm_query_bwd_segments over the SAME segment sizes in the same order with that plan;
- *                              workspace >= nmf_vm_walk_workspace_bytes(total M).
- * nmf_vm_query_bwd_segments = plan + planned walk inside one workspace (nmf_vm_bwd_workspace_bytes = the two sizes added). */
-int64_t nmf_vm_bin_plan_bytes(int64_t M, int32_t grid);
-int64_t nmf_vm_walk_workspace_bytes(int64_t M);
-int nmf_vm_bin_plan(const nmf_vm_params* p, const float* const* xyzt /*HOST array of device pointers*/,
-                    const int64_t* Ms /*HOST array*/, int32_t n_segs, void* plan, int64_t plan_bytes, void* stream);
-int nmf_vm_query_bwd_planned(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs /*HOST array*/, int32_t n_segs,
-                             const float* const dpk[3], const float* const dlk[3],
-                             const float* const app_planes[3], const float* const app_lines[3],
-                             const float* basis, float* const g_dpk[3], float* const g_dlk[3],
-                             float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                             const void* plan, int64_t plan_bytes, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Folds the packed gradient back onto the factors (transpose of nmf_vm_pack_density):
- * g_planes[i] [G][G][16], g_lines[i] [G][16] are OVERWRITTEN. */
-int nmf_vm_unpack_density_grad(const nmf_vm_params* p, const float* const g_dpk[3],
-                               const float* const g_dlk[3], float* const g_planes[3],
-                               float* const g_lines[3], void* stream);
-/* The same with the gradient of the density L1 term added in the same pass: g += l1_scale_dev[0] * sgn(x) / numel(x) for each of
- * the six density parameters x (fields/tensoRF.py:332-340 `density_L1`, weighted by train.py:640-677), given in the storage
- * order of the gradients.  Same bits as the unpack followed by nmf_l1_mean_bwd(accumulate), one launch less at the end of a step. */
-int nmf_vm_unpack_density_grad_l1(const nmf_vm_params* p, const float* const g_dpk[3], const float* const g_dlk[3],
-                                  float* const g_planes[3], float* const g_lines[3], const float* const x_planes[3],
-                                  const float* const x_lines[3], const float* l1_scale_dev, void* stream);
+ * g_planes[i] [G][G][16], g_lines[i] [G][16] are OVERWRITTEN.
+ * x_planes / x_lines / l1_scale_dev (all NULL or all set): the gradient of the density L1 term is added in the same pass,
+ * g += l1_scale_dev[0] * sgn(x) / numel(x) for each of the six density parameters x (fields/tensoRF.py:332-340 `density_L1`,
+ * weighted by train.py:640-677), given in the storage order of the gradients.  Same bits as the plain unpack followed by
+ * nmf_l1_mean_bwd(accumulate), one launch less at the end of a step. */
+int nmf_vm_unpack_density_grad(const nmf_vm_params* p, const float* const g_dpk[3], const float* const g_dlk[3],
+                               float* const g_planes[3], float* const g_lines[3], const float* const x_planes[3],
+                               const float* const x_lines[3], const float* l1_scale_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Compositing: raw2alpha (modules/tensor_nerf.py:19-35) and row_mask_sum
@@ -427,33 +387,34 @@ int nmf_heads_bwd(const float* feat, int64_t M, const float* W, const float* b, 
  * per K block, fp32 accumulation: fp32-class accuracy, csrc/brdf_mlp.hip).  Writes out [R][3] and, when act_mask is not
  * NULL, the ReLU masks of the two hidden layers for the backward: act_mask [R][4] uint32 = per ray {layer-1 mask,
  * layer-2 mask} of lane half 0, then of lane half 1 (bit 16 ub + q = unit 32 ub + (q & 3) + 8 (q >> 2) + 4 half). */
-int nmf_brdf_mlp_fwd(const float* W0, const float* b0, const float* W2, const float* b2, const float* W4,
+int nmf_brdf_mlp_fwd(const void* image, const float* W0, const float* b0, const float* W2, const float* b2, const float* W4,
                      const float* b4, const float* half_vec, const float* diff_vec, const float* feat_src,
                      const float* rough_src, const int32_t* src_idx, int64_t R, float out_bias, float* out,
-                     uint32_t* act_mask, int32_t max_workgroups /* 0 = default; see nmf_brdf_mlp_bwd */, void* stream);
-/* Backward of the call above for the SAME inputs: fwd_out [R][3] and act_mask [R][4] are that call's outputs (the
- * sigmoid adjoint and the ReLU decisions come from them; the hidden activations are recomputed per 32-ray tile as
- * values, two bf16 terms per operand).  d_feat [rows of feat_src][24] = adjoint of feat_src, ACCUMULATED (caller zeroes):
- * the adjoints of the rays that gathered a row (src_idx non-decreasing: consecutive rays) are summed inside the kernel,
- * one atomic per (row, column) run of a 32-ray tile.  gW* / gb* are ACCUMULATED (caller zeroes): gW0 [64][66], gb0 [64],
- * gW2 [64][64], gb2 [64], gW4 [4][64], gb4 [4] (row 3 of gW4 / gb4 stays untouched: the fourth output is unused).
- * max_workgroups: 0 = the kernel's own choice (one persistent workgroup per CU, fewer for short launches); > 0 caps
- * them, for callers that run this launch on a second stream NEXT TO other kernels and want it to leave CUs free for
- * them (the training pass: nmf_amd/fast_step.py, csrc/step_core.inc).
- * workspace (device, nmf_brdf_mlp_bwd_workspace_bytes(R, max_workgroups) bytes, need not be initialised): one partial
- * sum of the weight gradients per workgroup; a second small launch adds them in workgroup order, so a gradient element
+                     uint32_t* act_mask, int32_t max_workgroups /* 0 = default; see nmf_brdf_mlp_bwd_segments */, void* stream);
+/* The weights of the forward and of the backward are given as the six tensors (image = NULL) or as a PACKED IMAGE (R4; W0..b4
+ * are then not read): what the kernels stage into LDS in front of their first tile -- the split-bf16 planes of W0 | b0, W2
+ * (forward: three terms; backward: two terms plus W2^T and W0[:, :24]^T) and the fp32 rows of the last layer -- written once per
+ * weight update by nmf_brdf_mlp_pack (one launch of two workgroups) into nmf_brdf_mlp_image_bytes() bytes of device memory
+ * (16-byte aligned).  A launch then starts with a byte copy instead of the conversion (the parameters are those of
+ * modules/brdf.py:177-261's `self.mlp`, which change only in the optimizer step: train.py:733-735).  Results are bit-identical. */
+int64_t nmf_brdf_mlp_image_bytes(void);
+int nmf_brdf_mlp_pack(const float* W0, const float* b0, const float* W2, const float* b2, const float* W4, const float* b4,
+                      void* image, int64_t image_bytes, void* stream);
+/* Backward of nmf_brdf_mlp_fwd over ONE OR TWO ray sets in one launch (R4): the BRDF evaluations of a recursion level and of the
+ * level below it (models/microfacet.py:377-456 at recur 0 and 1) share the weights, and a launch costs ~25 us before and after its
+ * tiles whatever its size.  Sets with R = 0 are skipped.
+ * Per set, the SAME inputs as the forward; fwd_out [R][3] and act_mask [R][4] are that call's outputs (the sigmoid adjoint and the
+ * ReLU decisions come from them; the hidden activations are recomputed per 32-ray tile as values, two bf16 terms per operand).
+ * d_feat [rows of feat_src][24] = adjoint of feat_src, ACCUMULATED (caller zeroes): the adjoints of the rays that gathered a row
+ * (src_idx non-decreasing: consecutive rays) are summed inside the kernel, one atomic per (row, column) run of a 32-ray tile.
+ * gW* / gb* are ACCUMULATED (caller zeroes): gW0 [64][66], gb0 [64], gW2 [64][64], gb2 [64], gW4 [4][64], gb4 [4] (row 3 of gW4 /
+ * gb4 stays untouched: the fourth output is unused).
+ * max_workgroups: 0 = the kernel's own choice (one persistent workgroup per CU, fewer for short launches); > 0 caps them, for
+ * callers that run this launch on a second stream NEXT TO other kernels and want it to leave CUs free for them (the training
+ * pass: nmf_amd/fast_step.py, csrc/step_core.inc).
+ * workspace (device, nmf_brdf_mlp_bwd_segments_workspace_bytes(Rs, n_segs, max_workgroups) bytes, need not be initialised): one
+ * partial sum of the weight gradients per workgroup; a second small launch adds them in workgroup order, so a gradient element
  * receives one atomic per call instead of one per workgroup. */
-int nmf_brdf_mlp_bwd(const float* W0, const float* b0, const float* W2, const float* b2, const float* W4,
-                     const float* b4, const float* half_vec, const float* diff_vec, const float* feat_src,
-                     const float* rough_src, const int32_t* src_idx, int64_t R, const float* fwd_out,
-                     const uint32_t* act_mask, const float* d_out, float* d_feat, float* gW0, float* gb0,
-                     float* gW2, float* gb2, float* gW4, float* gb4, int32_t max_workgroups, void* workspace,
-                     int64_t workspace_bytes, void* stream);
-int64_t nmf_brdf_mlp_bwd_workspace_bytes(int64_t R, int32_t max_workgroups);
-/* The backward over ONE OR TWO ray sets in one launch (R4): the BRDF evaluations of a recursion level and of the level below it
- * (models/microfacet.py:377-456 at recur 0 and 1) share the weights, and a launch costs ~25 us before and after its tiles whatever
- * its size.  image: nmf_brdf_mlp_pack's output or NULL (then W0..b4 are read); per set the arguments of nmf_brdf_mlp_bwd; sets
- * with R = 0 are skipped.  Gradients as in nmf_brdf_mlp_bwd (ACCUMULATED).  Workspace: nmf_brdf_mlp_bwd_segments_workspace_bytes. */
 typedef struct nmf_mlp_bwd_segment {
     const float* half_vec;      /* [R][3] */
     const float* diff_vec;      /* [R][3] */
@@ -471,23 +432,6 @@ int nmf_brdf_mlp_bwd_segments(const void* image, const float* W0, const float* b
                               float* gW0, float* gb0, float* gW2, float* gb2, float* gW4, float* gb4, int32_t max_workgroups,
                               void* workspace, int64_t workspace_bytes, void* stream);
 int64_t nmf_brdf_mlp_bwd_segments_workspace_bytes(const int64_t* Rs /*HOST*/, int32_t n_segs, int32_t max_workgroups);
-/* The same two calls with the weights as a PACKED IMAGE (R4): what the kernels stage into LDS in front of their first tile --
- * the split-bf16 planes of W0 | b0, W2 (forward: three terms; backward: two terms plus W2^T and W0[:, :24]^T) and the fp32 rows
- * of the last layer -- written once per weight update by nmf_brdf_mlp_pack (one launch of two workgroups) into
- * nmf_brdf_mlp_image_bytes() bytes of device memory (16-byte aligned).  A launch then starts with a byte copy instead of the
- * conversion (the parameters are those of modules/brdf.py:177-261's `self.mlp`, which change only in the optimizer step:
- * train.py:733-735).  Results are bit-identical to the unpacked calls. */
-int64_t nmf_brdf_mlp_image_bytes(void);
-int nmf_brdf_mlp_pack(const float* W0, const float* b0, const float* W2, const float* b2, const float* W4, const float* b4,
-                      void* image, int64_t image_bytes, void* stream);
-int nmf_brdf_mlp_fwd_packed(const void* image, const float* half_vec, const float* diff_vec, const float* feat_src,
-                            const float* rough_src, const int32_t* src_idx, int64_t R, float out_bias, float* out,
-                            uint32_t* act_mask, int32_t max_workgroups, void* stream);
-int nmf_brdf_mlp_bwd_packed(const void* image, const float* half_vec, const float* diff_vec, const float* feat_src,
-                            const float* rough_src, const int32_t* src_idx, int64_t R, const float* fwd_out,
-                            const uint32_t* act_mask, const float* d_out, float* d_feat, float* gW0, float* gb0,
-                            float* gW2, float* gb2, float* gW4, float* gb4, int32_t max_workgroups, void* workspace,
-                            int64_t workspace_bytes, void* stream);
 /* out[s][0:D] = sum_{r in segment s} vals[r*row_stride + 0:D], D <= 64 (adjoint of the feature gather). */
 int nmf_segment_sum_wide(const float* vals, int64_t row_stride, int32_t D, const int64_t* offsets,
                          int64_t n_seg, float* out, void* stream);
@@ -500,22 +444,15 @@ int nmf_segment_sum_wide(const float* vals, int64_t row_stride, int32_t D, const
  * (row_off[Mb] = R), cnt_rows [>=Mb] their counts, inv [M] row of each sample or -1, totals = {R, Mb}.
  * bidx / row_off / cnt_rows are sized by the caller for the worst case (M, M+1, M).
  * xyzt_rows (optional, [>=Mb][4], needs xyzt [M][4]): xyzt_rows[row] = xyzt[bidx[row]], the sample positions of the rows
- * (microfacet.py:352: `xyzs[bounce_mask]`), written by the same pass instead of a gather launch behind the size read-back. */
-int nmf_bounce_index(const int32_t* counts, int64_t M, int32_t* bidx, int64_t* row_off, int32_t* cnt_rows,
-                     int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows, void* workspace,
-                     int64_t workspace_bytes, void* stream);
+ * (microfacet.py:352: `xyzs[bounce_mask]`), written by the same pass instead of a gather launch behind the size read-back.
+ * M_live (DEVICE, may be NULL): the live element count when it is still on the device (e.g. totals[0] of nmf_march_scan); the
+ * launch is sized by the bound M_cap, elements at or beyond *M_live are neither read nor written (see nmf_vm_query_fwd).
+ * publish_mapped_dev (may be NULL): [R, Mb, publish_seq] is also published into mapped host memory (see nmf_march_scan). */
+int nmf_bounce_index(const int32_t* counts, int64_t M_cap, const int64_t* M_live, int32_t* bidx, int64_t* row_off,
+                     int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows, void* workspace,
+                     int64_t workspace_bytes, void* publish_mapped_dev, int64_t publish_seq, void* stream);
 int64_t nmf_bounce_index_workspace_bytes(int64_t M);
-/* The same queries / index with the live element count still ON THE DEVICE (M_live: e.g. totals[0] of nmf_march_scan): the launch
- * is sized by the bound M_cap the caller allocated for (sampler.max_samples, samplers/alphagrid.py:353-364), elements at or beyond
- * *M_live are neither read nor written.  Lets a caller queue the level-0 pipeline behind the scan without waiting for its sizes. */
-int nmf_vm_query_fwd_live(const nmf_vm_params* p, const float* xyzt, int64_t M_cap, const int64_t* M_live,
-                          const void* const dpk[3], const void* const dlk[3], const void* const app_planes[3],
-                          const void* const app_lines[3], int32_t tables_bf16, const float* basis, float* sigma_feat,
-                          float* sigma, float* grad, float* normal, float* app, float* coef, void* stream);
-int nmf_bounce_index_live(const int32_t* counts, int64_t M_cap, const int64_t* M_live, int32_t* bidx, int64_t* row_off,
-                          int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows, void* workspace,
-                          int64_t workspace_bytes, void* publish_mapped_dev, int64_t publish_seq, void* stream);
-/* nmf_select_bounces + nmf_bounce_index_live in the launches of the latter (R4): the bounce count of a sample is one expression
+/* nmf_select_bounces + nmf_bounce_index in the launches of the latter (R4): the bounce count of a sample is one expression
  * of (weights[i], u[i]) (modules/pt_selectors.py:5-60; arguments as nmf_select_bounces), evaluated inside the index kernels
  * instead of by a launch of its own on the forward's chain.  counts are not materialised.  M_cap <= 2^20; M_live may be NULL. */
 int nmf_bounce_index_select(const float* weights, const float* u, int32_t mode, float mul, float add, float sum_w,
@@ -523,10 +460,6 @@ int nmf_bounce_index_select(const float* weights, const float* u, int32_t mode, 
                             int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows,
                             void* workspace, int64_t workspace_bytes, void* publish_mapped_dev, int64_t publish_seq,
                             void* stream);
-/* nmf_bounce_index that also publishes [R, Mb, publish_seq] into mapped host memory (see nmf_march_scan_publish). */
-int nmf_bounce_index_publish(const int32_t* counts, int64_t M, int32_t* bidx, int64_t* row_off, int32_t* cnt_rows,
-                             int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows, void* workspace,
-                             int64_t workspace_bytes, void* publish_mapped_dev, int64_t publish_seq, void* stream);
 /* Per bounce row (models/microfacet.py:297,304-316,352-361): V = -ray direction, N = normal facing V
  * (n * sign(V.n)), r1 = max(roughness, min_rough), f0, diffuse = albedo * E(n) with E the 9-term SH irradiance
  * (conv [9][3] DEVICE pointer, modules/sh.py:97-142), feat = app + anoise * feat_noise (feat_noise may be NULL),
@@ -657,10 +590,9 @@ typedef struct {
     int32_t is_f64;
     int32_t reserved;
 } nmf_adam_slot;
-int nmf_adam_step(const nmf_adam_slot* slots, int32_t n_slots, void* stream);
-/* The same update gated by a device float (e.g. the summed loss of the step): not finite -> no parameter and no moment changes.
- * train.py:704-705 skips a chunk whose loss is NaN after a host read-back; this keeps the decision on the device. */
-int nmf_adam_step_guarded(const nmf_adam_slot* slots, int32_t n_slots, const float* guard, void* stream);
+/* guard (DEVICE, may be NULL): the update is gated by that float (e.g. the summed loss of the step): not finite -> no parameter and
+ * no moment changes.  train.py:704-705 skips a chunk whose loss is NaN after a host read-back; this keeps the decision on the device. */
+int nmf_adam_step(const nmf_adam_slot* slots, int32_t n_slots, const float* guard, void* stream);
 
 /* Multi-tensor copy with fp32 <-> fp64 conversion, all slots in one launch (slots: HOST array, passed by value): packs the
  * per-parameter gradients into the flat fp32 all-reduce buffer and unpacks the reduced sums (ONE collective

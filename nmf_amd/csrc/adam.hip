@@ -160,11 +160,7 @@ extern "C" int nmf_multi_copy(const nmf_copy_slot* slots, int32_t n_slots, void*
     return NMF_OK;
 }
 
-extern "C" int nmf_adam_step(const nmf_adam_slot* slots, int32_t n_slots, void* stream) {
-    return nmf_adam_step_guarded(slots, n_slots, nullptr, stream);
-}
-
-extern "C" int nmf_adam_step_guarded(const nmf_adam_slot* slots, int32_t n_slots, const float* guard, void* stream) {
+extern "C" int nmf_adam_step(const nmf_adam_slot* slots, int32_t n_slots, const float* guard, void* stream) {
     NMF_REQUIRE(slots != nullptr || n_slots == 0, NMF_EINVAL, "nmf_adam_step: null slot table");
     NMF_REQUIRE(n_slots >= 0, NMF_EINVAL, "nmf_adam_step: negative slot count");
     for (int32_t i = 0; i < n_slots; ++i) {

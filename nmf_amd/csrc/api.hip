@@ -40,11 +40,6 @@ extern "C" int nmf_stream_wait_event(void* stream, void* event) {
     hipError_t r = hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0);
     return r == hipSuccess ? NMF_OK : nmf_fail((int)r, "nmf_stream_wait_event");
 }
-extern "C" int nmf_memcpy_d2h_async(void* dst_host, const void* src_dev, int64_t nbytes, void* stream) {
-    NMF_REQUIRE(dst_host && src_dev && nbytes >= 0, NMF_EINVAL, "nmf_memcpy_d2h_async: args");
-    hipError_t r = hipMemcpyAsync(dst_host, src_dev, (size_t)nbytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
-    return r == hipSuccess ? NMF_OK : nmf_fail((int)r, "nmf_memcpy_d2h_async");
-}
 extern "C" int nmf_event_create_timed(void** event) {
     NMF_REQUIRE(event, NMF_EINVAL, "nmf_event_create_timed: null");
     hipEvent_t e;
@@ -60,7 +55,7 @@ extern "C" int nmf_event_elapsed_ms(void* start, void* stop, float* ms) {
 }
 
 // ---- size read-back through host memory the device writes directly ----------------------------------------------------------
-// The event path (nmf_memcpy_d2h_async + nmf_event_record + nmf_event_synchronize) costs a copy command, a marker and the
+// An event path (an asynchronous copy to the host + nmf_event_record + nmf_event_synchronize) costs a copy command, a marker and the
 // runtime's signal wait per read-back.  Here the sizes are PUBLISHED: a one-thread kernel stores them into mapped, coherent
 // host memory followed by a sequence number, and the host spins on that number (nmf_wait_seq).
 namespace {

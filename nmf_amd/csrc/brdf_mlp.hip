@@ -975,9 +975,21 @@ static int set_lds_once(const void* fn, int bytes, const char* what) {
     return e == hipSuccess ? NMF_OK : nmf_fail((int)e, what);
 }
 
-static int mlp_fwd_impl(const MlpW& w, const void* image, const float* half_vec, const float* diff_vec, const float* feat_src,
-                        const float* rough_src, const int32_t* src_idx, int64_t R, float out_bias, float* out, uint32_t* act_mask,
-                        int32_t max_workgroups, void* stream) {
+// the weights of a call: a packed image (nmf_brdf_mlp_pack, 16-byte aligned) or, without one, the six tensors
+static bool weights_given(const void* image, const float* W0, const float* b0, const float* W2, const float* b2, const float* W4,
+                          const float* b4) {
+    const float* ws[6] = {W0, b0, W2, b2, W4, b4};
+    return image ? ((uintptr_t)image & 15) == 0 : check_w(ws) != 0;
+}
+
+extern "C" int nmf_brdf_mlp_fwd(const void* image, const float* W0, const float* b0, const float* W2, const float* b2,
+                                const float* W4, const float* b4, const float* half_vec, const float* diff_vec,
+                                const float* feat_src, const float* rough_src, const int32_t* src_idx, int64_t R, float out_bias,
+                                float* out, uint32_t* act_mask, int32_t max_workgroups, void* stream) {
+    NMF_REQUIRE(R >= 0, NMF_EINVAL, "nmf_brdf_mlp_fwd: R < 0");
+    if (R == 0) return NMF_OK;
+    NMF_REQUIRE(weights_given(image, W0, b0, W2, b2, W4, b4), NMF_EINVAL,
+                "nmf_brdf_mlp_fwd: a packed image (16-byte aligned) or the six weight tensors");
     NMF_REQUIRE(half_vec && diff_vec && feat_src && rough_src && out, NMF_EINVAL, "nmf_brdf_mlp_fwd: null");
     static const int lds = set_lds_once((const void*)k_brdf_mlp_fwd, FWD_LDS, "nmf_brdf_mlp_fwd: hipFuncSetAttribute");
     if (lds != NMF_OK) return lds;
@@ -985,23 +997,11 @@ static int mlp_fwd_impl(const MlpW& w, const void* image, const float* half_vec,
     int64_t cap = 256;                                  // one workgroup per CU (127 KB of LDS)
     if (max_workgroups > 0 && max_workgroups < cap) cap = max_workgroups;
     const unsigned grid = (unsigned)(wgs < cap ? wgs : cap);
-    NMF_LAUNCH(k_brdf_mlp_fwd, dim3(grid), dim3(64 * FWD_WAVES), FWD_LDS, (hipStream_t)stream, w, half_vec,
-                       diff_vec, feat_src, rough_src, src_idx, R, out_bias, out, reinterpret_cast<uint4*>(act_mask),
-                       static_cast<const uint4*>(image));
+    NMF_LAUNCH(k_brdf_mlp_fwd, dim3(grid), dim3(64 * FWD_WAVES), FWD_LDS, (hipStream_t)stream,
+                       image ? MlpW{} : MlpW{W0, b0, W2, b2, W4, b4}, half_vec, diff_vec, feat_src, rough_src, src_idx, R, out_bias,
+                       out, reinterpret_cast<uint4*>(act_mask), static_cast<const uint4*>(image));
     NMF_CHECK_LAUNCH("nmf_brdf_mlp_fwd");
     return NMF_OK;
-}
-
-extern "C" int nmf_brdf_mlp_fwd(const float* W0, const float* b0, const float* W2, const float* b2, const float* W4,
-                                const float* b4, const float* half_vec, const float* diff_vec, const float* feat_src,
-                                const float* rough_src, const int32_t* src_idx, int64_t R, float out_bias, float* out,
-                                uint32_t* act_mask, int32_t max_workgroups, void* stream) {
-    NMF_REQUIRE(R >= 0, NMF_EINVAL, "nmf_brdf_mlp_fwd: R < 0");
-    if (R == 0) return NMF_OK;
-    const float* ws[6] = {W0, b0, W2, b2, W4, b4};
-    NMF_REQUIRE(check_w(ws), NMF_EINVAL, "nmf_brdf_mlp_fwd: null");
-    return mlp_fwd_impl(MlpW{W0, b0, W2, b2, W4, b4}, nullptr, half_vec, diff_vec, feat_src, rough_src, src_idx, R, out_bias, out,
-                        act_mask, max_workgroups, stream);
 }
 
 extern "C" int64_t nmf_brdf_mlp_image_bytes(void) { return IMG_BYTES; }
@@ -1021,16 +1021,6 @@ extern "C" int nmf_brdf_mlp_pack(const float* W0, const float* b0, const float* 
     return NMF_OK;
 }
 
-extern "C" int nmf_brdf_mlp_fwd_packed(const void* image, const float* half_vec, const float* diff_vec, const float* feat_src,
-                                       const float* rough_src, const int32_t* src_idx, int64_t R, float out_bias, float* out,
-                                       uint32_t* act_mask, int32_t max_workgroups, void* stream) {
-    NMF_REQUIRE(R >= 0, NMF_EINVAL, "nmf_brdf_mlp_fwd_packed: R < 0");
-    if (R == 0) return NMF_OK;
-    NMF_REQUIRE(image && ((uintptr_t)image & 15) == 0, NMF_EINVAL, "nmf_brdf_mlp_fwd_packed: image null or not 16-byte aligned");
-    return mlp_fwd_impl(MlpW{}, image, half_vec, diff_vec, feat_src, rough_src, src_idx, R, out_bias, out, act_mask, max_workgroups,
-                        stream);
-}
-
 static unsigned bwd_grid_tiles(int64_t tiles, int32_t max_workgroups) {
     // One workgroup of 4 waves per CU (150 KB of LDS, one wave per SIMD).  Every workgroup stages the weight images
     // and writes a 37 KB partial, so short launches use fewer of them: at least 2 tiles per wave (45 k rays: 54 us against 63
@@ -1039,11 +1029,6 @@ static unsigned bwd_grid_tiles(int64_t tiles, int32_t max_workgroups) {
     int64_t cap = 256;
     if (max_workgroups > 0 && max_workgroups < cap) cap = max_workgroups;
     return (unsigned)(wgs < cap ? wgs : cap);
-}
-static unsigned bwd_grid(int64_t R, int32_t max_workgroups) { return bwd_grid_tiles(cdiv(R, RT), max_workgroups); }
-
-extern "C" int64_t nmf_brdf_mlp_bwd_workspace_bytes(int64_t R, int32_t max_workgroups) {
-    return R <= 0 ? 0 : (int64_t)bwd_grid(R, max_workgroups) * N_PERSIST * 64 * (int64_t)sizeof(float);
 }
 
 extern "C" int64_t nmf_brdf_mlp_bwd_segments_workspace_bytes(const int64_t* Rs, int32_t n_segs, int32_t max_workgroups) {
@@ -1056,13 +1041,13 @@ extern "C" int64_t nmf_brdf_mlp_bwd_segments_workspace_bytes(const int64_t* Rs, 
 static int mlp_bwd_launch(const MlpW& w, const void* image, const nmf_mlp_bwd_segment* segs, int n, float* gW0, float* gb0,
                           float* gW2, float* gb2, float* gW4, float* gb4, int32_t max_workgroups, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-    NMF_REQUIRE(gW0 && gb0 && gW2 && gb2 && gW4 && gb4, NMF_EINVAL, "nmf_brdf_mlp_bwd: null");
+    NMF_REQUIRE(gW0 && gb0 && gW2 && gb2 && gW4 && gb4, NMF_EINVAL, "nmf_brdf_mlp_bwd_segments: null");
     MlpBwdSegs G;
     int64_t tiles[2] = {0, 0};
     for (int i = 0; i < n; ++i) {
         const nmf_mlp_bwd_segment& q = segs[i];
         NMF_REQUIRE(q.half_vec && q.diff_vec && q.feat_src && q.rough_src && q.fwd_out && q.act_mask && q.d_out && q.d_feat,
-                    NMF_EINVAL, "nmf_brdf_mlp_bwd: null");
+                    NMF_EINVAL, "nmf_brdf_mlp_bwd_segments: null");
         G.s[i] = MlpBwdSeg{q.half_vec, q.diff_vec, q.feat_src, q.rough_src, q.src_idx, q.R, q.fwd_out,
                            reinterpret_cast<const uint4*>(q.act_mask), q.d_out, q.d_feat};
         tiles[i] = cdiv(q.R, RT);
@@ -1072,27 +1057,19 @@ static int mlp_bwd_launch(const MlpW& w, const void* image, const nmf_mlp_bwd_se
     G.n_tiles = tiles[0] + tiles[1];
     const unsigned grid = bwd_grid_tiles(G.n_tiles, max_workgroups);
     NMF_REQUIRE(workspace && workspace_bytes >= (int64_t)grid * N_PERSIST * 64 * (int64_t)sizeof(float), NMF_EINVAL,
-                "nmf_brdf_mlp_bwd: workspace too small (nmf_brdf_mlp_bwd_workspace_bytes)");
+                "nmf_brdf_mlp_bwd_segments: workspace too small (nmf_brdf_mlp_bwd_segments_workspace_bytes)");
     static_assert(BWD_WAVES * N_PERSIST * 64 * 4 <= BWD_LDS, "the per-wave sums fit into the kernel's LDS");
-    static const int lds = set_lds_once((const void*)k_brdf_mlp_bwd, BWD_LDS, "nmf_brdf_mlp_bwd: hipFuncSetAttribute");
+    static const int lds = set_lds_once((const void*)k_brdf_mlp_bwd, BWD_LDS, "nmf_brdf_mlp_bwd_segments: hipFuncSetAttribute");
     if (lds != NMF_OK) return lds;
     float* partials = static_cast<float*>(workspace);
     NMF_LAUNCH(k_brdf_mlp_bwd, dim3(grid), dim3(64 * BWD_WAVES), BWD_LDS, (hipStream_t)stream, w, G, partials,
                        static_cast<const uint4*>(image));
-    NMF_CHECK_LAUNCH("nmf_brdf_mlp_bwd");
+    NMF_CHECK_LAUNCH("nmf_brdf_mlp_bwd_segments");
     static_assert((N_PERSIST * 64) % 32 == 0, "k_brdf_mlp_reduce takes 32 elements per workgroup");
     NMF_LAUNCH(k_brdf_mlp_reduce, dim3(N_PERSIST * 64 / 32), dim3(256), 0, (hipStream_t)stream, partials, (int)grid, gW0,
                        gb0, gW2, gb2, gW4, gb4);
-    NMF_CHECK_LAUNCH("nmf_brdf_mlp_bwd (reduce)");
+    NMF_CHECK_LAUNCH("nmf_brdf_mlp_bwd_segments (reduce)");
     return NMF_OK;
-}
-
-static int mlp_bwd_impl(const MlpW& w, const void* image, const float* half_vec, const float* diff_vec, const float* feat_src,
-                        const float* rough_src, const int32_t* src_idx, int64_t R, const float* fwd_out, const uint32_t* act_mask,
-                        const float* d_out, float* d_feat, float* gW0, float* gb0, float* gW2, float* gb2, float* gW4, float* gb4,
-                        int32_t max_workgroups, void* workspace, int64_t workspace_bytes, void* stream) {
-    const nmf_mlp_bwd_segment seg{half_vec, diff_vec, feat_src, rough_src, src_idx, R, fwd_out, act_mask, d_out, d_feat};
-    return mlp_bwd_launch(w, image, &seg, 1, gW0, gb0, gW2, gb2, gW4, gb4, max_workgroups, workspace, workspace_bytes, stream);
 }
 
 extern "C" int nmf_brdf_mlp_bwd_segments(const void* image, const float* W0, const float* b0, const float* W2, const float* b2,
@@ -1100,8 +1077,7 @@ extern "C" int nmf_brdf_mlp_bwd_segments(const void* image, const float* W0, con
                                          float* gW0, float* gb0, float* gW2, float* gb2, float* gW4, float* gb4,
                                          int32_t max_workgroups, void* workspace, int64_t workspace_bytes, void* stream) {
     NMF_REQUIRE(segs && n_segs >= 1 && n_segs <= 2, NMF_EINVAL, "nmf_brdf_mlp_bwd_segments: one or two ray sets");
-    const float* ws[6] = {W0, b0, W2, b2, W4, b4};
-    NMF_REQUIRE((image && ((uintptr_t)image & 15) == 0) || check_w(ws), NMF_EINVAL,
+    NMF_REQUIRE(weights_given(image, W0, b0, W2, b2, W4, b4), NMF_EINVAL,
                 "nmf_brdf_mlp_bwd_segments: a packed image (16-byte aligned) or the six weight tensors");
     nmf_mlp_bwd_segment live[2];
     int n = 0;
@@ -1112,30 +1088,4 @@ extern "C" int nmf_brdf_mlp_bwd_segments(const void* image, const float* W0, con
     if (n == 0) return NMF_OK;
     return mlp_bwd_launch(image ? MlpW{} : MlpW{W0, b0, W2, b2, W4, b4}, image, live, n, gW0, gb0, gW2, gb2, gW4, gb4, max_workgroups,
                           workspace, workspace_bytes, stream);
-}
-
-extern "C" int nmf_brdf_mlp_bwd(const float* W0, const float* b0, const float* W2, const float* b2, const float* W4,
-                                const float* b4, const float* half_vec, const float* diff_vec, const float* feat_src,
-                                const float* rough_src, const int32_t* src_idx, int64_t R, const float* fwd_out,
-                                const uint32_t* act_mask, const float* d_out, float* d_feat, float* gW0, float* gb0,
-                                float* gW2, float* gb2, float* gW4, float* gb4, int32_t max_workgroups, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-    NMF_REQUIRE(R >= 0, NMF_EINVAL, "nmf_brdf_mlp_bwd: R < 0");
-    if (R == 0) return NMF_OK;
-    const float* ws[6] = {W0, b0, W2, b2, W4, b4};
-    NMF_REQUIRE(check_w(ws), NMF_EINVAL, "nmf_brdf_mlp_bwd: null");
-    return mlp_bwd_impl(MlpW{W0, b0, W2, b2, W4, b4}, nullptr, half_vec, diff_vec, feat_src, rough_src, src_idx, R, fwd_out, act_mask,
-                        d_out, d_feat, gW0, gb0, gW2, gb2, gW4, gb4, max_workgroups, workspace, workspace_bytes, stream);
-}
-
-extern "C" int nmf_brdf_mlp_bwd_packed(const void* image, const float* half_vec, const float* diff_vec, const float* feat_src,
-                                       const float* rough_src, const int32_t* src_idx, int64_t R, const float* fwd_out,
-                                       const uint32_t* act_mask, const float* d_out, float* d_feat, float* gW0, float* gb0,
-                                       float* gW2, float* gb2, float* gW4, float* gb4, int32_t max_workgroups, void* workspace,
-                                       int64_t workspace_bytes, void* stream) {
-    NMF_REQUIRE(R >= 0, NMF_EINVAL, "nmf_brdf_mlp_bwd_packed: R < 0");
-    if (R == 0) return NMF_OK;
-    NMF_REQUIRE(image && ((uintptr_t)image & 15) == 0, NMF_EINVAL, "nmf_brdf_mlp_bwd_packed: image null or not 16-byte aligned");
-    return mlp_bwd_impl(MlpW{}, image, half_vec, diff_vec, feat_src, rough_src, src_idx, R, fwd_out, act_mask, d_out, d_feat, gW0,
-                        gb0, gW2, gb2, gW4, gb4, max_workgroups, workspace, workspace_bytes, stream);
 }

@@ -182,9 +182,9 @@ std::tuple<Tensor, Tensor, Tensor> march_scan(const Tensor& counts, int64_t max_
     Tensor offsets = ie(counts, {B + 1}, at::kLong), whole = ie(counts, {B}, at::kByte), totals = ie(counts, {2}, at::kLong);
     const int64_t nbytes = nmf_march_scan_workspace_bytes(B);
     Tensor ws = ie(counts, {nbytes / 8}, at::kLong);
-    check(nmf_march_scan_publish(i32(counts), B, max_samples, static_cast<int64_t*>(offsets.data_ptr()),
-                                 static_cast<uint8_t*>(whole.data_ptr()), static_cast<int64_t*>(totals.data_ptr()), ws.data_ptr(),
-                                 nbytes, reinterpret_cast<void*>(pub), pub_seq, st(stream)),
+    check(nmf_march_scan(i32(counts), B, max_samples, static_cast<int64_t*>(offsets.data_ptr()),
+                         static_cast<uint8_t*>(whole.data_ptr()), static_cast<int64_t*>(totals.data_ptr()), ws.data_ptr(), nbytes,
+                         reinterpret_cast<void*>(pub), pub_seq, st(stream)),
           "nmf_march_scan");
     return {offsets, whole, totals};
 }
@@ -209,7 +209,7 @@ std::tuple<OT, OT, OT, OT, OT, OT> vm_query_fwd(int64_t p_addr, const Tensor& xy
                                                 const std::vector<Tensor>& dlk, const std::vector<Tensor>& apl,
                                                 const std::vector<Tensor>& ali, const OT& basis, bool want_density,
                                                 bool want_normal, bool want_app, bool want_coef, int64_t stream, int64_t live = 0) {
-    // live: device address of the sample count when xyzt is sized by a bound (nmf_vm_query_fwd_live)
+    // live: device address of the sample count when xyzt is sized by a bound (M_live of nmf_vm_query_fwd)
     TimedScope _ts(__func__, stream);
     const auto* p = reinterpret_cast<const nmf_vm_params*>(p_addr);
     const int64_t M = xyzt.size(0);
@@ -220,42 +220,22 @@ std::tuple<OT, OT, OT, OT, OT, OT> vm_query_fwd(int64_t p_addr, const Tensor& xy
     if (want_coef) cf = fe(xyzt, {M, 72});
     const bool need_d = want_density || want_normal, need_a = want_app || want_coef;
     auto o = [](OT& t) { return t.has_value() ? static_cast<float*>(t->data_ptr()) : nullptr; };
+    // fp32 tables or bfloat16 copies of them (BASELINE configs[1]; fp32 arithmetic): one dtype for all tables of a call
     const bool bf16 = (need_d ? dpk : apl).at(0).scalar_type() == at::kBFloat16;
-    if (live) {
-        const void *a[3], *b[3], *c[3], *d[3];
-        for (int i = 0; i < 3; ++i) {
-            a[i] = need_d ? vptr(dpk.at(i)) : nullptr;
-            b[i] = need_d ? vptr(dlk.at(i)) : nullptr;
-            c[i] = need_a ? vptr(apl.at(i)) : nullptr;
-            d[i] = need_a ? vptr(ali.at(i)) : nullptr;
-        }
-        check(nmf_vm_query_fwd_live(p, f32(xyzt), M, reinterpret_cast<const int64_t*>(live), need_d ? a : nullptr, need_d ? b : nullptr,
-                                    need_a ? c : nullptr, need_a ? d : nullptr, bf16 ? 1 : 0, need_a ? of32(basis) : nullptr, o(sf),
-                                    o(sg), o(gr), o(nr), o(ap), o(cf), st(stream)),
-              "nmf_vm_query_fwd_live");
-        return {sf, sg, gr, nr, ap, cf};
+    auto h = [bf16](const Tensor& t) -> const void* {
+        return bf16 ? static_cast<const void*>(ptr<const uint16_t>(t, at::kBFloat16)) : static_cast<const void*>(f32(t));
+    };
+    const void *a[3], *b[3], *c[3], *d[3];
+    if ((need_d && (dpk.size() != 3 || dlk.size() != 3)) || (need_a && (apl.size() != 3 || ali.size() != 3))) fail("expected three tensors");
+    for (int i = 0; i < 3; ++i) {
+        a[i] = need_d ? h(dpk[i]) : nullptr;
+        b[i] = need_d ? h(dlk[i]) : nullptr;
+        c[i] = need_a ? h(apl[i]) : nullptr;
+        d[i] = need_a ? h(ali[i]) : nullptr;
     }
-    if (bf16) {        // bfloat16 copies of the tables (BASELINE configs[1]); fp32 arithmetic
-        const uint16_t *a[3], *b[3], *c[3], *d[3];
-        auto h = [](const Tensor& t) { return ptr<const uint16_t>(t, at::kBFloat16); };
-        for (int i = 0; i < 3; ++i) {
-            a[i] = need_d ? h(dpk.at(i)) : nullptr;
-            b[i] = need_d ? h(dlk.at(i)) : nullptr;
-            c[i] = need_a ? h(apl.at(i)) : nullptr;
-            d[i] = need_a ? h(ali.at(i)) : nullptr;
-        }
-        check(nmf_vm_query_fwd_bf16(p, f32(xyzt), M, need_d ? a : nullptr, need_d ? b : nullptr, need_a ? c : nullptr,
-                                    need_a ? d : nullptr, need_a ? of32(basis) : nullptr, o(sf), o(sg), o(gr), o(nr), o(ap), o(cf),
-                                    st(stream)),
-              "nmf_vm_query_fwd_bf16");
-        return {sf, sg, gr, nr, ap, cf};
-    }
-    P3 a{}, b{}, c{}, d{};
-    if (need_d) { a = three(dpk); b = three(dlk); }
-    if (need_a) { c = three(apl); d = three(ali); }
-    check(nmf_vm_query_fwd(p, f32(xyzt), M, need_d ? a.p : nullptr, need_d ? b.p : nullptr, need_a ? c.p : nullptr,
-                           need_a ? d.p : nullptr, need_a ? of32(basis) : nullptr, o(sf), o(sg), o(gr), o(nr), o(ap), o(cf),
-                           st(stream)),
+    check(nmf_vm_query_fwd(p, f32(xyzt), M, reinterpret_cast<const int64_t*>(live), need_d ? a : nullptr, need_d ? b : nullptr,
+                           need_a ? c : nullptr, need_a ? d : nullptr, bf16 ? 1 : 0, need_a ? of32(basis) : nullptr, o(sf), o(sg),
+                           o(gr), o(nr), o(ap), o(cf), st(stream)),
           "nmf_vm_query_fwd");
     return {sf, sg, gr, nr, ap, cf};
 }
@@ -338,18 +318,12 @@ std::tuple<Tensor, Tensor> brdf_mlp_fwd(const std::vector<Tensor>& w, const Tens
     Tensor o = fe(half_vec, {R, 3});
     Tensor mask;
     if (with_mask) mask = ie(half_vec, {R, 4}, at::kInt);
-    if (packed)
-        check(nmf_brdf_mlp_fwd_packed(image->data_ptr(), f32(half_vec), f32(diff_vec), f32(feat_src), f32(rough_src),
-                                      optr<const int32_t>(src_idx, at::kInt), R, (float)out_bias, out(o),
-                                      with_mask ? static_cast<uint32_t*>(mask.data_ptr()) : nullptr, (int32_t)max_workgroups,
-                                      st(stream)),
-              "nmf_brdf_mlp_fwd_packed");
-    else
-        check(nmf_brdf_mlp_fwd(f32(w[0]), f32(w[1]), f32(w[2]), f32(w[3]), f32(w[4]), f32(w[5]), f32(half_vec), f32(diff_vec),
-                               f32(feat_src), f32(rough_src), optr<const int32_t>(src_idx, at::kInt), R, (float)out_bias, out(o),
-                               with_mask ? static_cast<uint32_t*>(mask.data_ptr()) : nullptr, (int32_t)max_workgroups,
-                               st(stream)),
-              "nmf_brdf_mlp_fwd");
+    auto wp = [&](int i) { return packed ? nullptr : f32(w[i]); };
+    check(nmf_brdf_mlp_fwd(packed ? image->data_ptr() : nullptr, wp(0), wp(1), wp(2), wp(3), wp(4), wp(5), f32(half_vec),
+                           f32(diff_vec), f32(feat_src), f32(rough_src), optr<const int32_t>(src_idx, at::kInt), R, (float)out_bias,
+                           out(o), with_mask ? static_cast<uint32_t*>(mask.data_ptr()) : nullptr, (int32_t)max_workgroups,
+                           st(stream)),
+          "nmf_brdf_mlp_fwd");
     return {o, mask};
 }
 
@@ -430,11 +404,11 @@ py::tuple bounce_index(const Tensor& counts, const OT& xyzt, int64_t stream, int
     Tensor ws = ie(counts, {nbytes / 8}, at::kLong);
     Tensor rows;
     if (xyzt.has_value()) rows = at::empty({M1, 4}, counts.options().dtype(at::kFloat));
-    check(nmf_bounce_index_live(M ? i32(counts) : nullptr, M, reinterpret_cast<const int64_t*>(live), static_cast<int32_t*>(bidx.data_ptr()),
-                                   static_cast<int64_t*>(row_off.data_ptr()), static_cast<int32_t*>(cnt_rows.data_ptr()),
-                                   static_cast<int32_t*>(inv.data_ptr()), static_cast<int64_t*>(totals.data_ptr()),
-                                   (xyzt.has_value() && M) ? f32(*xyzt) : nullptr, xyzt.has_value() ? out(rows) : nullptr,
-                                   ws.data_ptr(), nbytes, reinterpret_cast<void*>(pub), pub_seq, st(stream)),
+    check(nmf_bounce_index(M ? i32(counts) : nullptr, M, reinterpret_cast<const int64_t*>(live), static_cast<int32_t*>(bidx.data_ptr()),
+                           static_cast<int64_t*>(row_off.data_ptr()), static_cast<int32_t*>(cnt_rows.data_ptr()),
+                           static_cast<int32_t*>(inv.data_ptr()), static_cast<int64_t*>(totals.data_ptr()),
+                           (xyzt.has_value() && M) ? f32(*xyzt) : nullptr, xyzt.has_value() ? out(rows) : nullptr,
+                           ws.data_ptr(), nbytes, reinterpret_cast<void*>(pub), pub_seq, st(stream)),
           "nmf_bounce_index");
     if (xyzt.has_value()) return py::make_tuple(bidx, row_off, cnt_rows, inv.narrow(0, 0, M), totals, rows);
     return py::make_tuple(bidx, row_off, cnt_rows, inv.narrow(0, 0, M), totals);
@@ -600,37 +574,8 @@ void sat_lookup_bwd_table(const Tensor& sat, const Tensor& dirs, const Tensor& s
           "nmf_sat_lookup_bwd_binned");
 }
 
-Tensor brdf_mlp_bwd(const std::vector<Tensor>& w, const Tensor& half_vec, const Tensor& diff_vec, const Tensor& feat_src,
-                    const Tensor& rough_src, const OT& src_idx, const Tensor& fwd_out, const Tensor& act_mask,
-                    const Tensor& d_out, const std::vector<Tensor>& grads, int64_t max_workgroups, int64_t stream,
-                    const OT& image = c10::nullopt) {
-    TimedScope _ts(__func__, stream);
-    const bool packed = image.has_value() && image->defined();
-    if ((!packed && w.size() != 6) || grads.size() != 6) fail("brdf_mlp_bwd: six weight / gradient tensors expected");
-    const int64_t R = half_vec.size(0);
-    Tensor d_feat = at::zeros({feat_src.size(0), 24}, half_vec.options().dtype(at::kFloat));      // summed per row of feat_src
-    Tensor go = d_out.contiguous();
-    float* g[6];
-    for (int i = 0; i < 6; ++i) g[i] = static_cast<float*>(vptr(grads[i]));
-    const int64_t nws = nmf_brdf_mlp_bwd_workspace_bytes(R, (int32_t)max_workgroups);
-    Tensor ws = fe(half_vec, {std::max<int64_t>(nws, 4) / 4});
-    if (packed)
-        check(nmf_brdf_mlp_bwd_packed(image->data_ptr(), f32(half_vec), f32(diff_vec), f32(feat_src), f32(rough_src),
-                                      optr<const int32_t>(src_idx, at::kInt), R, f32(fwd_out),
-                                      static_cast<const uint32_t*>(act_mask.data_ptr()), f32(go), out(d_feat), g[0], g[1], g[2], g[3],
-                                      g[4], g[5], (int32_t)max_workgroups, out(ws), nws, st(stream)),
-              "nmf_brdf_mlp_bwd_packed");
-    else
-        check(nmf_brdf_mlp_bwd(f32(w[0]), f32(w[1]), f32(w[2]), f32(w[3]), f32(w[4]), f32(w[5]), f32(half_vec), f32(diff_vec),
-                               f32(feat_src), f32(rough_src), optr<const int32_t>(src_idx, at::kInt), R, f32(fwd_out),
-                               static_cast<const uint32_t*>(act_mask.data_ptr()), f32(go), out(d_feat), g[0], g[1], g[2], g[3], g[4],
-                               g[5], (int32_t)max_workgroups, out(ws), nws, st(stream)),
-              "nmf_brdf_mlp_bwd");
-    return d_feat;
-}
-
-// the same over ONE OR TWO ray sets in one launch (nmf_brdf_mlp_bwd_segments); a set = {half_vec, diff_vec, feat_src, rough_src,
-// src_idx, fwd_out, act_mask, d_out}; -> d_feat per set
+// the BRDF MLP's backward over ONE OR TWO ray sets in one launch (nmf_brdf_mlp_bwd_segments); a set = {half_vec, diff_vec, feat_src,
+// rough_src, src_idx, fwd_out, act_mask, d_out}; -> d_feat per set (zero-initialised: summed per row of feat_src)
 using MlpSet = std::tuple<Tensor, Tensor, Tensor, Tensor, OT, Tensor, Tensor, Tensor>;
 std::vector<Tensor> brdf_mlp_bwd_sets(const std::vector<Tensor>& w, const std::vector<MlpSet>& sets, const std::vector<Tensor>& grads,
                                       int64_t max_workgroups, int64_t stream, const OT& image = c10::nullopt) {
@@ -663,6 +608,14 @@ std::vector<Tensor> brdf_mlp_bwd_sets(const std::vector<Tensor>& w, const std::v
                                     (int32_t)max_workgroups, out(ws), nws, st(stream)),
           "nmf_brdf_mlp_bwd_segments");
     return outs;
+}
+
+Tensor brdf_mlp_bwd(const std::vector<Tensor>& w, const Tensor& half_vec, const Tensor& diff_vec, const Tensor& feat_src,
+                    const Tensor& rough_src, const OT& src_idx, const Tensor& fwd_out, const Tensor& act_mask,
+                    const Tensor& d_out, const std::vector<Tensor>& grads, int64_t max_workgroups, int64_t stream,
+                    const OT& image = c10::nullopt) {
+    return brdf_mlp_bwd_sets(w, {MlpSet{half_vec, diff_vec, feat_src, rough_src, src_idx, fwd_out, act_mask, d_out}}, grads,
+                             max_workgroups, stream, image)[0];
 }
 
 Tensor heads_bwd(const Tensor& feat, const Tensor& W, const Tensor& b, const std::vector<double>& hp, const Tensor& d_out,
@@ -752,32 +705,16 @@ std::tuple<Tensor, OT, OT> ray_compose_bwd(const Tensor& weight, const OT& refl_
 // ---- field backward (FieldGrads.backward: two walks + the unpack, ~180 us of Python per step) -------------------------
 using Seg = std::tuple<Tensor, OT, OT, OT, OT, OT, OT>;     // xyzt, sigma_feat, grad, d_sigma, d_sigma_feat, d_normal, d_app
 
-// the brick sort of a walk, built from the positions alone (nmf_vm_bin_plan): -> opaque plan buffer
-Tensor vm_bin_plan(int64_t p_addr, const std::vector<Tensor>& xyzts, int64_t stream, const OT& into = OT()) {
+// clean: the zero scratch a caller keeps between walks (uint8, nmf_vm_bwd_clean_bytes); absent: the walk zeroes its counters itself
+void vm_query_bwd_segments(int64_t p_addr, const std::vector<Seg>& segs, const std::vector<Tensor>& dpk,
+                           const std::vector<Tensor>& dlk, const std::vector<Tensor>& apl, const std::vector<Tensor>& ali,
+                           const OT& basis, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
+                           const std::vector<Tensor>& g_apl, const std::vector<Tensor>& g_ali, const OT& g_basis, const OT& clean,
+                           int64_t stream) {
     TimedScope _ts(__func__, stream);
-    const auto* p = reinterpret_cast<const nmf_vm_params*>(p_addr);
-    if (xyzts.empty() || xyzts.size() > NMF_VM_MAX_SEGMENTS) fail("vm_bin_plan: 1.." + std::to_string(NMF_VM_MAX_SEGMENTS) + " segments");
-    const float* ptrs[NMF_VM_MAX_SEGMENTS];
-    int64_t Ms[NMF_VM_MAX_SEGMENTS], M = 0;
-    for (size_t i = 0; i < xyzts.size(); ++i) {
-        ptrs[i] = f32(xyzts[i]);
-        Ms[i] = xyzts[i].size(0);
-        M += Ms[i];
-    }
-    const int64_t nbytes = nmf_vm_bin_plan_bytes(M, p->grid);
-    Tensor plan = into.has_value() ? *into : ie(xyzts[0], {(nbytes + 3) / 4}, at::kInt);
-    if (plan.numel() * plan.element_size() < nbytes) fail("vm_bin_plan: the buffer passed in is too small");
-    check(nmf_vm_bin_plan(p, ptrs, Ms, (int32_t)xyzts.size(), plan.data_ptr(), nbytes, st(stream)), "nmf_vm_bin_plan");
-    return plan;
-}
-
-void vm_query_bwd_impl(const char* name, int64_t p_addr, const std::vector<Seg>& segs, const std::vector<Tensor>& dpk,
-                       const std::vector<Tensor>& dlk, const std::vector<Tensor>& apl, const std::vector<Tensor>& ali,
-                       const OT& basis, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
-                       const std::vector<Tensor>& g_apl, const std::vector<Tensor>& g_ali, const OT& g_basis, const OT& plan,
-                       int64_t stream, const OT& clean = c10::nullopt) {
-    // clean: the kept zero scratch of nmf_vm_query_bwd_segments_clean (a walk without a plan)
-    TimedScope _ts(name, stream);
+    const bool kept = clean.has_value() && clean->defined();
+    if (kept && (clean->scalar_type() != at::kByte || !clean->is_contiguous() || !clean->is_cuda()))
+        fail("vm_query_bwd_segments: the clean scratch must be a contiguous device uint8 tensor");
     const auto* p = reinterpret_cast<const nmf_vm_params*>(p_addr);
     if (segs.size() > NMF_VM_MAX_SEGMENTS) fail("at most " + std::to_string(NMF_VM_MAX_SEGMENTS) + " segments per walk");
     nmf_vm_bwd_segment arr[NMF_VM_MAX_SEGMENTS];
@@ -798,7 +735,7 @@ void vm_query_bwd_impl(const char* name, int64_t p_addr, const std::vector<Seg>&
         want_a = want_a || std::get<6>(segs[i]).has_value();
     }
     if (M == 0) return;
-    const int64_t nbytes = plan.has_value() ? nmf_vm_walk_workspace_bytes(M) : nmf_vm_bwd_workspace_bytes(M, p->grid);
+    const int64_t nbytes = nmf_vm_bwd_workspace_bytes(M, p->grid);
     Tensor ws = ie(std::get<0>(segs[0]), {(nbytes + 3) / 4}, at::kInt);
     P3 a{}, b{}, c{}, d{};
     float *ga[3] = {nullptr, nullptr, nullptr}, *gb[3] = {nullptr, nullptr, nullptr}, *gc[3] = {nullptr, nullptr, nullptr},
@@ -809,56 +746,16 @@ void vm_query_bwd_impl(const char* name, int64_t p_addr, const std::vector<Seg>&
     };
     if (want_d) { a = three(dpk); b = three(dlk); three_out(g_dpk, ga); three_out(g_dlk, gb); }
     if (want_a) { c = three(apl); d = three(ali); three_out(g_apl, gc); three_out(g_ali, gd); }
-    if (plan.has_value())
-        check(nmf_vm_query_bwd_planned(p, arr, (int32_t)segs.size(), want_d ? a.p : nullptr, want_d ? b.p : nullptr,
-                                       want_a ? c.p : nullptr, want_a ? d.p : nullptr, want_a ? of32(basis) : nullptr,
-                                       want_d ? ga : nullptr, want_d ? gb : nullptr, want_a ? gc : nullptr, want_a ? gd : nullptr,
-                                       want_a ? static_cast<float*>(vptr(g_basis)) : nullptr, vptr(plan), plan->numel() * 4,
-                                       ws.data_ptr(), nbytes, st(stream)),
-              "nmf_vm_query_bwd_planned");
-    else if (clean.has_value() && clean->defined())
-        check(nmf_vm_query_bwd_segments_clean(p, arr, (int32_t)segs.size(), want_d ? a.p : nullptr, want_d ? b.p : nullptr,
-                                              want_a ? c.p : nullptr, want_a ? d.p : nullptr, want_a ? of32(basis) : nullptr,
-                                              want_d ? ga : nullptr, want_d ? gb : nullptr, want_a ? gc : nullptr, want_a ? gd : nullptr,
-                                              want_a ? static_cast<float*>(vptr(g_basis)) : nullptr, clean->data_ptr(), clean->numel(),
-                                              ws.data_ptr(), nbytes, st(stream)),
-              "nmf_vm_query_bwd_segments_clean");
-    else
-        check(nmf_vm_query_bwd_segments(p, arr, (int32_t)segs.size(), want_d ? a.p : nullptr, want_d ? b.p : nullptr,
-                                        want_a ? c.p : nullptr, want_a ? d.p : nullptr, want_a ? of32(basis) : nullptr,
-                                        want_d ? ga : nullptr, want_d ? gb : nullptr, want_a ? gc : nullptr, want_a ? gd : nullptr,
-                                        want_a ? static_cast<float*>(vptr(g_basis)) : nullptr, ws.data_ptr(), nbytes, st(stream)),
-              "nmf_vm_query_bwd_segments");
-}
-
-void vm_query_bwd_segments(int64_t p_addr, const std::vector<Seg>& segs, const std::vector<Tensor>& dpk,
-                           const std::vector<Tensor>& dlk, const std::vector<Tensor>& apl, const std::vector<Tensor>& ali,
-                           const OT& basis, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
-                           const std::vector<Tensor>& g_apl, const std::vector<Tensor>& g_ali, const OT& g_basis,
-                           int64_t stream) {
-    vm_query_bwd_impl(__func__, p_addr, segs, dpk, dlk, apl, ali, basis, g_dpk, g_dlk, g_apl, g_ali, g_basis, OT(), stream);
-}
-
-void vm_query_bwd_clean(int64_t p_addr, const std::vector<Seg>& segs, const std::vector<Tensor>& dpk,
-                        const std::vector<Tensor>& dlk, const std::vector<Tensor>& apl, const std::vector<Tensor>& ali,
-                        const OT& basis, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
-                        const std::vector<Tensor>& g_apl, const std::vector<Tensor>& g_ali, const OT& g_basis,
-                        const Tensor& clean, int64_t stream) {
-    if (clean.scalar_type() != at::kByte || !clean.is_contiguous() || !clean.is_cuda()) fail("vm_query_bwd_clean: scratch must be a device uint8 tensor");
-    vm_query_bwd_impl("vm_query_bwd_segments", p_addr, segs, dpk, dlk, apl, ali, basis, g_dpk, g_dlk, g_apl, g_ali, g_basis, OT(), stream,
-                      OT(clean));
-}
-
-void vm_query_bwd_planned(int64_t p_addr, const std::vector<Seg>& segs, const std::vector<Tensor>& dpk,
-                          const std::vector<Tensor>& dlk, const std::vector<Tensor>& apl, const std::vector<Tensor>& ali,
-                          const OT& basis, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
-                          const std::vector<Tensor>& g_apl, const std::vector<Tensor>& g_ali, const OT& g_basis,
-                          const Tensor& plan, int64_t stream) {
-    vm_query_bwd_impl(__func__, p_addr, segs, dpk, dlk, apl, ali, basis, g_dpk, g_dlk, g_apl, g_ali, g_basis, OT(plan), stream);
+    check(nmf_vm_query_bwd_segments(p, arr, (int32_t)segs.size(), want_d ? a.p : nullptr, want_d ? b.p : nullptr,
+                                    want_a ? c.p : nullptr, want_a ? d.p : nullptr, want_a ? of32(basis) : nullptr,
+                                    want_d ? ga : nullptr, want_d ? gb : nullptr, want_a ? gc : nullptr, want_a ? gd : nullptr,
+                                    want_a ? static_cast<float*>(vptr(g_basis)) : nullptr, kept ? clean->data_ptr() : nullptr,
+                                    kept ? clean->numel() : 0, ws.data_ptr(), nbytes, st(stream)),
+          "nmf_vm_query_bwd_segments");
 }
 
 // out: the (gp, gl) of an earlier call, overwritten; l1: (the six density parameters in the gradients' storage order, 0-d device
-// scale) -- the gradient of scale * sum_i mean |x_i| is added in the same launch (nmf_vm_unpack_density_grad_l1)
+// scale) -- the gradient of scale * sum_i mean |x_i| is added in the same launch
 using Lists2 = std::tuple<std::vector<Tensor>, std::vector<Tensor>>;
 Lists2 vm_unpack_density_grad(int64_t p_addr, const std::vector<Tensor>& g_dpk, const std::vector<Tensor>& g_dlk,
                               const c10::optional<Lists2>& into, const c10::optional<std::tuple<std::vector<Tensor>, Tensor>>& l1,
@@ -886,21 +783,20 @@ Lists2 vm_unpack_density_grad(int64_t p_addr, const std::vector<Tensor>& g_dpk, 
         op[i] = const_cast<float*>(dense_f32(gp[i]));
         ol[i] = const_cast<float*>(dense_f32(gl[i]));
     }
+    const float *xp[3], *xl[3];
     if (l1.has_value()) {
         const std::vector<Tensor>& xs = std::get<0>(*l1);
         if (xs.size() != 6) fail("vm_unpack_density_grad: l1 = (six density parameters, scale)");
-        const float *xp[3], *xl[3];
         for (int i = 0; i < 3; ++i) {
             if (xs[i].numel() != gp[i].numel() || xs[3 + i].numel() != gl[i].numel())
                 fail("vm_unpack_density_grad: parameter / gradient size mismatch");
             xp[i] = dense_f32(xs[i]);
             xl[i] = dense_f32(xs[3 + i]);
         }
-        check(nmf_vm_unpack_density_grad_l1(p, a.p, b.p, op, ol, xp, xl, f32(std::get<1>(*l1)), st(stream)),
-              "nmf_vm_unpack_density_grad_l1");
-    } else {
-        check(nmf_vm_unpack_density_grad(p, a.p, b.p, op, ol, st(stream)), "nmf_vm_unpack_density_grad");
     }
+    check(nmf_vm_unpack_density_grad(p, a.p, b.p, op, ol, l1.has_value() ? xp : nullptr, l1.has_value() ? xl : nullptr,
+                                     l1.has_value() ? f32(std::get<1>(*l1)) : nullptr, st(stream)),
+          "nmf_vm_unpack_density_grad");
     return {gp, gl};
 }
 
@@ -1071,7 +967,7 @@ std::tuple<Tensor, Tensor> bounce_prep_heads_bwd(const Tensor& bidx, const Tenso
 // slot tables are ctypes arrays owned by the Python side: passed by address
 void adam_step(int64_t slots_addr, int64_t n, const OT& guard, int64_t stream) {
     TimedScope _ts(__func__, stream);
-    check(nmf_adam_step_guarded(reinterpret_cast<const nmf_adam_slot*>(slots_addr), (int32_t)n, of32(guard), st(stream)),
+    check(nmf_adam_step(reinterpret_cast<const nmf_adam_slot*>(slots_addr), (int32_t)n, of32(guard), st(stream)),
           "nmf_adam_step");
 }
 void multi_copy(int64_t slots_addr, int64_t n, int64_t stream) {
@@ -1264,11 +1160,12 @@ PYBIND11_MODULE(_nmf_host, m) {
     m.def("march_fill", &march_fill);
     using OV = c10::optional<std::vector<Tensor>>;          // None for the tables of the half that is not asked for
     m.def("vm_query_fwd", [](int64_t p_addr, const Tensor& xyzt, const OV& dpk, const OV& dlk, const OV& apl, const OV& ali, const OT& basis,
-                             bool want_density, bool want_normal, bool want_app, bool want_coef, int64_t stream) {
+                             bool want_density, bool want_normal, bool want_app, bool want_coef, int64_t stream, int64_t live) {
         const std::vector<Tensor> none;
         return vm_query_fwd(p_addr, xyzt, dpk ? *dpk : none, dlk ? *dlk : none, apl ? *apl : none, ali ? *ali : none, basis,
-                            want_density, want_normal, want_app, want_coef, stream, 0);
-    });
+                            want_density, want_normal, want_app, want_coef, stream, live);
+    }, py::arg("p_addr"), py::arg("xyzt"), py::arg("dpk"), py::arg("dlk"), py::arg("apl"), py::arg("ali"), py::arg("basis"),
+       py::arg("want_density"), py::arg("want_normal"), py::arg("want_app"), py::arg("want_coef"), py::arg("stream"), py::arg("live") = 0);
     m.def("composite_fwd", &composite_fwd);
     m.def("segment_sum", &segment_sum);
     m.def("sat_lookup_fwd", &sat_lookup_fwd);
@@ -1305,9 +1202,6 @@ PYBIND11_MODULE(_nmf_host, m) {
     m.def("shade_mix_bwd", &shade_mix_bwd);
     m.def("ray_compose_bwd", &ray_compose_bwd);
     m.def("vm_query_bwd_segments", &vm_query_bwd_segments);
-    m.def("vm_query_bwd_planned", &vm_query_bwd_planned);
-    m.def("vm_query_bwd_clean", &vm_query_bwd_clean);
-    m.def("vm_bin_plan", &vm_bin_plan, py::arg("p_addr"), py::arg("xyzts"), py::arg("stream"), py::arg("into") = py::none());
     m.def("vm_unpack_density_grad", &vm_unpack_density_grad);
     m.def("adam_step", &adam_step);
     m.def("multi_copy", &multi_copy);

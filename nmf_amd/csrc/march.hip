@@ -847,14 +847,7 @@ extern "C" int64_t nmf_march_scan_workspace_bytes(int64_t B) {
 
 extern "C" int nmf_march_scan(const int32_t* counts, int64_t B, int64_t max_samples, int64_t* offsets,
                               uint8_t* whole_valid, int64_t* totals, void* workspace, int64_t workspace_bytes,
-                              void* stream) {
-    return nmf_march_scan_publish(counts, B, max_samples, offsets, whole_valid, totals, workspace, workspace_bytes, nullptr, 0,
-                                  stream);
-}
-
-extern "C" int nmf_march_scan_publish(const int32_t* counts, int64_t B, int64_t max_samples, int64_t* offsets,
-                                      uint8_t* whole_valid, int64_t* totals, void* workspace, int64_t workspace_bytes,
-                                      void* publish_mapped_dev, int64_t publish_seq, void* stream) {
+                              void* publish_mapped_dev, int64_t publish_seq, void* stream) {
     int64_t* pub = static_cast<int64_t*>(publish_mapped_dev);
     NMF_REQUIRE(counts && offsets && whole_valid && totals && B > 0, NMF_EINVAL, "nmf_march_scan: null/empty");
     const int64_t n_chunks = cdiv(B, SCAN_CHUNK);

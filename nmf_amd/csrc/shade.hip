@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(IDX_CHUNK) k_idx_partial(const int32_t* __rest
                                                           int64_t* __restrict__ chunk_sum, const int64_t* __restrict__ M_live,
                                                           SelectArgs sel) {
     __shared__ int64_t ws[17];
-    if (M_live && *M_live < M) M = *M_live;          // (the launch was sized by a bound: nmf_bounce_index_live)
+    if (M_live && *M_live < M) M = *M_live;          // (the launch was sized by a bound: M_live of nmf_bounce_index)
     const int64_t i = (int64_t)blockIdx.x * IDX_CHUNK + threadIdx.x;
     const int32_t c = i < M ? bounce_count(sel, counts, i) : 0;
     const int64_t v = c > 0 ? ((int64_t)c + ((int64_t)1 << FLAG_SHIFT)) : 0;
@@ -492,28 +492,13 @@ __global__ void __launch_bounds__(256) k_bg_adjoint(const float* __restrict__ ac
 
 extern "C" int64_t nmf_bounce_index_workspace_bytes(int64_t M) { return (cdiv(M > 0 ? M : 1, IDX_CHUNK) + 1) * 8; }
 
-extern "C" int nmf_bounce_index(const int32_t* counts, int64_t M, int32_t* bidx, int64_t* row_off,
-                                int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows,
-                                void* workspace, int64_t workspace_bytes, void* stream) {
-    return nmf_bounce_index_live(counts, M, nullptr, bidx, row_off, cnt_rows, inv, totals, xyzt, xyzt_rows, workspace, workspace_bytes,
-                                 nullptr, 0, stream);
-}
-
-extern "C" int nmf_bounce_index_publish(const int32_t* counts, int64_t M, int32_t* bidx, int64_t* row_off,
-                                        int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows,
-                                        void* workspace, int64_t workspace_bytes, void* publish_mapped_dev,
-                                        int64_t publish_seq, void* stream) {
-    return nmf_bounce_index_live(counts, M, nullptr, bidx, row_off, cnt_rows, inv, totals, xyzt, xyzt_rows, workspace, workspace_bytes,
-                                 publish_mapped_dev, publish_seq, stream);
-}
-
 static int bounce_index_impl(const int32_t* counts, SelectArgs sel, int64_t M, const int64_t* M_live, int32_t* bidx, int64_t* row_off,
                              int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows, void* workspace,
                              int64_t workspace_bytes, void* publish_mapped_dev, int64_t publish_seq, void* stream);
-extern "C" int nmf_bounce_index_live(const int32_t* counts, int64_t M, const int64_t* M_live, int32_t* bidx, int64_t* row_off,
-                                     int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows,
-                                     void* workspace, int64_t workspace_bytes, void* publish_mapped_dev,
-                                     int64_t publish_seq, void* stream) {
+extern "C" int nmf_bounce_index(const int32_t* counts, int64_t M, const int64_t* M_live, int32_t* bidx, int64_t* row_off,
+                                int32_t* cnt_rows, int32_t* inv, int64_t* totals, const float* xyzt, float* xyzt_rows,
+                                void* workspace, int64_t workspace_bytes, void* publish_mapped_dev, int64_t publish_seq,
+                                void* stream) {
     NMF_REQUIRE(counts || M == 0, NMF_EINVAL, "nmf_bounce_index: null");
     return bounce_index_impl(counts, SelectArgs{nullptr, nullptr, 0, 0.f, 0.f, 0.f, nullptr}, M, M_live, bidx, row_off, cnt_rows, inv, totals,
                              xyzt, xyzt_rows, workspace, workspace_bytes, publish_mapped_dev, publish_seq, stream);
@@ -551,7 +536,7 @@ static int bounce_index_impl(const int32_t* counts, SelectArgs sel, int64_t M, c
     NMF_REQUIRE(workspace_bytes >= nmf_bounce_index_workspace_bytes(M), NMF_EINVAL, "nmf_bounce_index: workspace too small");
     NMF_REQUIRE(n_chunks <= (1 << 22), NMF_ERANGE, "nmf_bounce_index: M too large");
     int64_t* chunk = static_cast<int64_t*>(workspace);
-    NMF_REQUIRE(!M_live || n_chunks <= IDX_CHUNK, NMF_ERANGE, "nmf_bounce_index_live: bound too large for a device-side count");
+    NMF_REQUIRE(!M_live || n_chunks <= IDX_CHUNK, NMF_ERANGE, "nmf_bounce_index: bound too large for a device-side count (M_live)");
     NMF_LAUNCH(k_idx_partial, dim3((unsigned)n_chunks), dim3(IDX_CHUNK), 0, st, counts, M, chunk, M_live, sel);
     if (n_chunks <= IDX_CHUNK) {
         NMF_LAUNCH(k_idx_final_fused, dim3((unsigned)n_chunks), dim3(IDX_CHUNK), 0, st, counts, M, chunk,

@@ -31,7 +31,7 @@ struct RuntimeEvent {
 };
 
 // two int64 sizes from the device to the host: the producing kernel PUBLISHES them into mapped, coherent host memory followed by a
-// sequence number (nmf_march_scan_publish / nmf_bounce_index_publish) and the host spins on that number (nmf_wait_seq) -- no copy
+// sequence number (the publish arguments of nmf_march_scan / nmf_bounce_index) and the host spins on that number (nmf_wait_seq) -- no copy
 // command, no marker, no runtime signal wait.
 struct SizeReadback {
     void* host = nullptr;
@@ -327,7 +327,7 @@ class StepCore {
     // that fill and clear the scratch would leave it non-zero: the scratch is dropped then, the next walk allocates a zeroed one.
     void walk_segments(std::vector<Seg>& segs, const OT& gb, int64_t stream) {
         // (R5: the brick sorts of the two walks that end the backward built as plans on an idle stream at the START of the backward --
-        //  nmf_vm_bin_plan, the walks then only permute their adjoints -- took 108 us of kernels off the tail and gave them back in the
+        //  the walks then only permuted their adjoints -- took 108 us of kernels off the tail and gave them back in the
         //  saturated window before it: in-process A/B 1.328 -> 1.341 ms, removed.  R4 had the same result with the plans under the forward.)
         const auto* vp = reinterpret_cast<const nmf_vm_params*>(vm_p);
         const int64_t nb = nmf_vm_bwd_clean_bytes(vp->grid);
@@ -335,7 +335,7 @@ class StepCore {
         Tensor& c = walk_clean_[walk_clean_i_++];
         if (!c.defined() || c.numel() != nb) c = at::zeros({nb}, std::get<0>(segs[0]).options().dtype(at::kByte));
         try {
-            vm_query_bwd_clean(vm_p, segs, dpk, dlk, apl, ali, basis, g_dpk, g_dlk, g_apl, g_ali, gb, c, stream);
+            vm_query_bwd_segments(vm_p, segs, dpk, dlk, apl, ali, basis, g_dpk, g_dlk, g_apl, g_ali, gb, c, stream);
         } catch (...) {
             c = Tensor();
             throw;

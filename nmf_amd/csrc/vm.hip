@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(256) k_vm_fwd(nmf_vm_params p, const float4* _
         for (int i = threadIdx.x; i < AD * 3 * CA; i += 256) s_basis[i] = basis[i];
         __syncthreads();
     }
-    // M_live: the sample count still lives on the device (the launch was sized by a bound: nmf_vm_query_fwd_live)
+    // M_live: the sample count still lives on the device (the launch was sized by a bound: nmf_vm_query_fwd with M_live)
     if (m >= M || (M_live && m >= *M_live)) return;
     const int G = p.grid;
     float xn[3];
@@ -694,12 +694,10 @@ __device__ __forceinline__ int seg_of(const Segs& sg, int64_t m, int64_t& local)
     return k;
 }
 
-// ---- the sort as a PLAN (R4): it depends on the sample positions alone, which the forward knows ----------------------
-// The three walks of a training step used to redo histogram + scan + atomic scatter inside the backward (300 us of kernel
-// time per step, 80 of them in the serial tail of the step).  nmf_vm_bin_plan runs these once, as soon as the positions
-// exist (on a side stream under the forward), with ONE atomic pass: the counter add of the histogram already returns the
-// sample's rank inside its (brick, counter copy), so slot[m] = start(brick, copy) + rank once the scan has run -- no
-// second pass of cursor atomics.  What is left for the backward is k_brick_records: one permuted 16-byte store per sample.
+// ---- the brick sort of a walk (R4) --------------------------------------------------------------------------------------
+// ONE atomic pass: the counter add of the histogram already returns the sample's rank inside its (brick, counter copy), so the
+// sample's place in brick order is start(brick, copy) + rank once the scan has run (k_place_records) -- no second pass of
+// cursor atomics.
 __global__ void __launch_bounds__(256) k_plan_hist(nmf_vm_params p, Segs sg, int64_t M, int nbx, int kc,
                                                    int32_t* __restrict__ counts, int2* __restrict__ keyrank) {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -720,19 +718,6 @@ __global__ void __launch_bounds__(256) k_plan_hist(nmf_vm_params p, Segs sg, int
     if (r.head) base = atomicAdd(counts + key, r.len);
     base = __shfl(base, lane_id() - r.off, 64);
     if (active) keyrank[m] = make_int2(key, base + r.off);
-}
-
-__global__ void __launch_bounds__(256) k_plan_place(Segs sg, int64_t M, const int2* __restrict__ keyrank,
-                                                    const int32_t* __restrict__ cursor, int32_t* __restrict__ slot,
-                                                    float4* __restrict__ rec0) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    const int2 kr = keyrank[m];
-    const int pos = cursor[kr.x] + kr.y;
-    slot[m] = pos;
-    int64_t l;
-    const int k = seg_of(sg, m, l);
-    rec0[pos] = reinterpret_cast<const float4*>(pick4(sg.xyzt, k))[l];
 }
 
 // Exclusive scan of the n brick counts -> offsets[n+1], the scatter cursors, and the work-item list of the backward walk:
@@ -862,7 +847,7 @@ constexpr unsigned long long SC_READY = 1ull << 63;
 
 // clean: the counters are handed back ZERO (every workgroup clears the counters of its own chunk once it has read them; the chunk
 // words are cleared by the launch that follows, see k_place_records) -- a caller that keeps the scratch between calls then needs no
-// memset launch in front of the next histogram (nmf_vm_query_bwd_segments_clean).
+// memset launch in front of the next histogram (the `clean` argument of nmf_vm_query_bwd_segments).
 __global__ void __launch_bounds__(SC_THREADS) k_bins_scan(int32_t* counts, int n, int kc,
                                                           unsigned long long* __restrict__ state, int32_t* __restrict__ offsets,
                                                           int32_t* __restrict__ cursor, int item, int2* __restrict__ items,
@@ -1022,33 +1007,10 @@ __device__ __forceinline__ float4 sample_adjoint_finish(const nmf_vm_params& p, 
     }
     return make_float4(dsf, dg0, dg1, dg2);
 }
-__device__ __forceinline__ float4 sample_adjoint(const nmf_vm_params& p, const Segs& sg, int k, int64_t l) {
-    return sample_adjoint_finish(p, sg, sample_adjoint_load(sg, k, l));
-}
 
 // The per-sample inputs of the backward walk, written in SORTED order so that the brick kernels stream them without an
-// indirection: rec1 = (adjoint of the raw density feature, adjoint of the raw density gradient); APP: the d_app row (its
-// 72 coefficient adjoints follow in k_dcoef).  slot[] and the sorted positions rec0 come from the plan.
-template <bool APP>
-__global__ void __launch_bounds__(256) k_brick_records(nmf_vm_params p, Segs sg, const int32_t* __restrict__ slot, int64_t M,
-                                                       float4* __restrict__ rec1, float* __restrict__ d_app_sorted) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    const int pos = slot[m];
-    int64_t l;
-    const int k = seg_of(sg, m, l);
-    rec1[pos] = sample_adjoint(p, sg, k, l);
-    if constexpr (APP) {
-        float da[AD];
-        load_run<AD / 4>(pick4(sg.d_app, k) + l * AD, da);
-        float4* srt = reinterpret_cast<float4*>(d_app_sorted + (int64_t)pos * AD);
-#pragma unroll
-        for (int q = 0; q < AD / 4; ++q) srt[q] = make_float4(da[4 * q], da[4 * q + 1], da[4 * q + 2], da[4 * q + 3]);
-    }
-}
-
-// place + records in one pass, for a walk that sorts inside its own call (no plan from the forward): the slot of a sample is used
-// where it is computed, so slot[] is neither written nor read and the launch between the two is gone
+// indirection: rec0 = the position, rec1 = (adjoint of the raw density feature, adjoint of the raw density gradient); APP: the
+// d_app row (its 72 coefficient adjoints follow in k_dcoef).  The place of a sample is used where it is computed.
 template <bool APP>
 __global__ void __launch_bounds__(256) k_place_records(nmf_vm_params p, Segs sg, int64_t M, const int2* __restrict__ keyrank,
                                                        const int32_t* __restrict__ cursor, float4* __restrict__ rec0,
@@ -1576,23 +1538,12 @@ extern "C" int nmf_vm_pack_density(const nmf_vm_params* p, const float* const pl
     return NMF_OK;
 }
 
-static int unpack_impl(const nmf_vm_params* p, const float* const g_dpk[3], const float* const g_dlk[3], float* const g_planes[3],
-                       float* const g_lines[3], const float* const x_planes[3], const float* const x_lines[3], const float* l1,
-                       void* stream);
-extern "C" int nmf_vm_unpack_density_grad(const nmf_vm_params* p, const float* const g_dpk[3],
-                                          const float* const g_dlk[3], float* const g_planes[3],
-                                          float* const g_lines[3], void* stream) {
-    return unpack_impl(p, g_dpk, g_dlk, g_planes, g_lines, nullptr, nullptr, nullptr, stream);
-}
-extern "C" int nmf_vm_unpack_density_grad_l1(const nmf_vm_params* p, const float* const g_dpk[3], const float* const g_dlk[3],
-                                             float* const g_planes[3], float* const g_lines[3], const float* const x_planes[3],
-                                             const float* const x_lines[3], const float* l1_scale_dev, void* stream) {
-    NMF_REQUIRE(all3(x_planes) && all3(x_lines) && l1_scale_dev, NMF_EINVAL, "nmf_vm_unpack_density_grad_l1: null");
-    return unpack_impl(p, g_dpk, g_dlk, g_planes, g_lines, x_planes, x_lines, l1_scale_dev, stream);
-}
-static int unpack_impl(const nmf_vm_params* p, const float* const g_dpk[3], const float* const g_dlk[3], float* const g_planes[3],
-                       float* const g_lines[3], const float* const x_planes[3], const float* const x_lines[3], const float* l1,
-                       void* stream) {
+extern "C" int nmf_vm_unpack_density_grad(const nmf_vm_params* p, const float* const g_dpk[3], const float* const g_dlk[3],
+                                          float* const g_planes[3], float* const g_lines[3], const float* const x_planes[3],
+                                          const float* const x_lines[3], const float* l1_scale_dev, void* stream) {
+    const bool l1 = x_planes || x_lines || l1_scale_dev;
+    NMF_REQUIRE(!l1 || (all3(x_planes) && all3(x_lines) && l1_scale_dev), NMF_EINVAL,
+                "nmf_vm_unpack_density_grad: x_planes / x_lines / l1_scale_dev must be all null or all set");
     NMF_REQUIRE(p && all3(g_dpk) && all3(g_dlk) && all3m(g_planes) && all3m(g_lines), NMF_EINVAL,
                 "nmf_vm_unpack_density_grad: null");
     const int G = p->grid;
@@ -1604,7 +1555,7 @@ static int unpack_impl(const nmf_vm_params* p, const float* const g_dpk[3], cons
     }
     L1Six q;
     for (int i = 0; i < 3; ++i) { q.x[i] = x_planes ? x_planes[i] : nullptr; q.x[3 + i] = x_lines ? x_lines[i] : nullptr; }
-    q.l1 = l1;
+    q.l1 = l1_scale_dev;
     NMF_LAUNCH(k_unpack_tables, dim3((unsigned)cdiv(n, 256), 6), dim3(256), 0, (hipStream_t)stream, *p, a, q);
     NMF_CHECK_LAUNCH("nmf_vm_unpack_density_grad");
     return NMF_OK;
@@ -1618,10 +1569,10 @@ static PtrsT3<TT> mkT(const TT* const a[3], bool on) {
 }
 
 template <class TT>
-static int vm_query_fwd_impl(const char* what, const nmf_vm_params* p, const float* xyzt, int64_t M, const TT* const dpk[3],
+static int vm_query_fwd_impl(const nmf_vm_params* p, const float* xyzt, int64_t M, const int64_t* M_live, const TT* const dpk[3],
                              const TT* const dlk[3], const TT* const app_planes[3], const TT* const app_lines[3],
                              const float* basis, float* sigma_feat, float* sigma, float* grad, float* normal, float* app,
-                             float* coef, void* stream, const int64_t* M_live = nullptr) {
+                             float* coef, void* stream) {
     NMF_REQUIRE(p && M >= 0, NMF_EINVAL, "nmf_vm_query_fwd: params");
     if (M == 0) return NMF_OK;
     NMF_REQUIRE(xyzt, NMF_EINVAL, "nmf_vm_query_fwd: xyzt null");
@@ -1633,46 +1584,37 @@ static int vm_query_fwd_impl(const char* what, const nmf_vm_params* p, const flo
                             app_lines[1] && app_lines[2] && (!app || basis)),
                 NMF_EINVAL, "nmf_vm_query_fwd: appearance tables missing");
     NMF_REQUIRE(!M_live || (want_d && (grad || normal)), NMF_EINVAL,
-                "nmf_vm_query_fwd_live: only the general query (density with gradient / normal) takes a device-side count");
+                "nmf_vm_query_fwd: only the general query (density with gradient / normal) takes a device-side count (M_live)");
     if (want_d && !want_a && !grad && !normal) {      // density value only
         NMF_LAUNCH_NAMED(sizeof(TT) == 4 ? "k_vm_sigma<float>" : "k_vm_sigma<unsigned short>", k_vm_sigma<TT>, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, *p,
                            (const float4*)xyzt, M, mkT<TT>(dpk, true), mkT<TT>(dlk, true), DP, DL, sigma_feat, sigma);
-        NMF_CHECK_LAUNCH(what);
+        NMF_CHECK_LAUNCH("nmf_vm_query_fwd");
         return NMF_OK;
     }
     if (!want_d && app && !coef) {      // appearance of the bounce rows: 8 lanes per row
         NMF_LAUNCH_NAMED(sizeof(TT) == 4 ? "k_vm_app_rows<float>" : "k_vm_app_rows<unsigned short>", k_vm_app_rows<TT>, dim3((unsigned)cdiv(M, APP_ROWS)), dim3(256), 0, (hipStream_t)stream, *p,
                            (const float4*)xyzt, M, mkT<TT>(app_planes, true), mkT<TT>(app_lines, true), basis, app);
-        NMF_CHECK_LAUNCH(what);
+        NMF_CHECK_LAUNCH("nmf_vm_query_fwd");
         return NMF_OK;
     }
     NMF_LAUNCH_NAMED(sizeof(TT) == 4 ? "k_vm_fwd<float>" : "k_vm_fwd<unsigned short>", k_vm_fwd<TT>, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream, *p,
                        (const float4*)xyzt, M, mkT<TT>(dpk, want_d), mkT<TT>(dlk, want_d), mkT<TT>(app_planes, want_a),
                        mkT<TT>(app_lines, want_a), basis, sigma_feat, sigma, grad, normal, app, coef, M_live);
-    NMF_CHECK_LAUNCH(what);
+    NMF_CHECK_LAUNCH("nmf_vm_query_fwd");
     return NMF_OK;
 }
 
-extern "C" int nmf_vm_query_fwd(const nmf_vm_params* p, const float* xyzt, int64_t M, const float* const dpk[3],
-                                const float* const dlk[3], const float* const app_planes[3],
-                                const float* const app_lines[3], const float* basis, float* sigma_feat, float* sigma,
-                                float* grad, float* normal, float* app, float* coef, void* stream) {
-    return vm_query_fwd_impl<float>("nmf_vm_query_fwd", p, xyzt, M, dpk, dlk, app_planes, app_lines, basis, sigma_feat, sigma,
-                                    grad, normal, app, coef, stream);
-}
-
-extern "C" int nmf_vm_query_fwd_live(const nmf_vm_params* p, const float* xyzt, int64_t M_cap, const int64_t* M_live,
-                                     const void* const dpk[3], const void* const dlk[3], const void* const app_planes[3],
-                                     const void* const app_lines[3], int32_t tables_bf16, const float* basis, float* sigma_feat,
-                                     float* sigma, float* grad, float* normal, float* app, float* coef, void* stream) {
-    NMF_REQUIRE(M_live, NMF_EINVAL, "nmf_vm_query_fwd_live: M_live null");
+extern "C" int nmf_vm_query_fwd(const nmf_vm_params* p, const float* xyzt, int64_t M_cap, const int64_t* M_live,
+                                const void* const dpk[3], const void* const dlk[3], const void* const app_planes[3],
+                                const void* const app_lines[3], int32_t tables_bf16, const float* basis, float* sigma_feat,
+                                float* sigma, float* grad, float* normal, float* app, float* coef, void* stream) {
     if (tables_bf16)
-        return vm_query_fwd_impl<uint16_t>("nmf_vm_query_fwd_live", p, xyzt, M_cap, (const uint16_t* const*)dpk, (const uint16_t* const*)dlk,
+        return vm_query_fwd_impl<uint16_t>(p, xyzt, M_cap, M_live, (const uint16_t* const*)dpk, (const uint16_t* const*)dlk,
                                            (const uint16_t* const*)app_planes, (const uint16_t* const*)app_lines, basis, sigma_feat,
-                                           sigma, grad, normal, app, coef, stream, M_live);
-    return vm_query_fwd_impl<float>("nmf_vm_query_fwd_live", p, xyzt, M_cap, (const float* const*)dpk, (const float* const*)dlk,
+                                           sigma, grad, normal, app, coef, stream);
+    return vm_query_fwd_impl<float>(p, xyzt, M_cap, M_live, (const float* const*)dpk, (const float* const*)dlk,
                                     (const float* const*)app_planes, (const float* const*)app_lines, basis, sigma_feat, sigma, grad,
-                                    normal, app, coef, stream, M_live);
+                                    normal, app, coef, stream);
 }
 
 extern "C" int nmf_vm_query_sigma(const nmf_vm_params* p, const float* xyzt, int64_t M, const void* const planes[3],
@@ -1721,27 +1663,18 @@ extern "C" int nmf_vm_query_rows(const nmf_vm_params* p, const float* xyzt, int6
     return NMF_OK;
 }
 
-extern "C" int nmf_vm_query_fwd_bf16(const nmf_vm_params* p, const float* xyzt, int64_t M, const uint16_t* const dpk[3],
-                                     const uint16_t* const dlk[3], const uint16_t* const app_planes[3],
-                                     const uint16_t* const app_lines[3], const float* basis, float* sigma_feat,
-                                     float* sigma, float* grad, float* normal, float* app, float* coef, void* stream) {
-    return vm_query_fwd_impl<uint16_t>("nmf_vm_query_fwd_bf16", p, xyzt, M, dpk, dlk, app_planes, app_lines, basis,
-                                       sigma_feat, sigma, grad, normal, app, coef, stream);
-}
-
 // counter copies per brick (power of two; measured on S1: 1 -> 64 us, 4 -> 45 us, 8 -> 64 us of binning per 0.88 M
 // samples, the scan growing with the copies): 4 while the single-workgroup scan over [brick][copy] stays short
 static int bin_copies(int64_t nb) {
     return nb <= 32768 ? 4 : 1;
 }
 
-// ---- layout of a plan (nmf_vm_bin_plan) and of the scratch of the walk itself ------------------------------------------
+// ---- layout of the brick sort (the front of the workspace) and of the scratch of the walk itself ------------------------------
 namespace {
 struct PlanLayout {
     int nbx, nb, kc, item_size, n_chunks;
     int64_t max_items;
     int2* keyrank;        // [M]   (brick * kc + counter copy, rank inside it)
-    int32_t* slot;        // [M]   position of sample m in brick order
     int32_t* counts;      // [(nb+1)*kc]
     unsigned long long* scan_state;   // [1 + n_scan_chunks]: ticket, chunk words of k_bins_scan (behind the counters: one memset)
     int n_scan_chunks;
@@ -1766,7 +1699,6 @@ PlanLayout plan_layout(void* base, int64_t M, int32_t grid) {
     L.n_chunks = (L.nb + SB_CHUNK - 1) / SB_CHUNK;
     uintptr_t q = up16((uintptr_t)base);
     L.keyrank = (int2*)q;                q = up16(q + sizeof(int2) * M);
-    L.slot = (int32_t*)q;                q = up16(q + sizeof(int32_t) * M);
     L.counts = (int32_t*)q;              q = up16(q + sizeof(int32_t) * (size_t)(L.nb + 1) * L.kc);
     L.n_scan_chunks = (L.nb + SC_CHUNK - 1) / SC_CHUNK;
     L.scan_state = (unsigned long long*)q;   q = up16(q + sizeof(unsigned long long) * (size_t)(L.n_scan_chunks + 1));
@@ -1780,7 +1712,7 @@ PlanLayout plan_layout(void* base, int64_t M, int32_t grid) {
     L.bytes = (int64_t)(q - (uintptr_t)base) + 16;
     return L;
 }
-// the scratch a caller may keep between walks (nmf_vm_query_bwd_segments_clean): zero on entry, zero again on exit
+// the scratch a caller may keep between walks (`clean` of nmf_vm_query_bwd_segments): zero on entry, zero again on exit
 struct CleanLayout {
     int32_t* counts;
     unsigned long long* scan_state;
@@ -1834,16 +1766,16 @@ int64_t gather_segments(const nmf_vm_bwd_segment* segs, int32_t n_segs, Segs& sg
     return M;
 }
 
-// place = false: the caller follows with k_place_records (the walk that sorts inside its own call)
+// histogram + scan; the caller follows with k_place_records
 // clean: L.counts / L.scan_state point into the caller's kept scratch (zero now, zero again afterwards): no memset
-int launch_plan(const nmf_vm_params* p, const Segs& sg, int64_t M, const PlanLayout& L, hipStream_t st, bool place, bool clean = false) {
+int launch_plan(const nmf_vm_params* p, const Segs& sg, int64_t M, const PlanLayout& L, hipStream_t st, bool clean) {
     // the look-back needs its chunks' workgroups resident together: 2048 of them fit the chip (8 per CU); grids beyond ~500^3 take
     // the two-launch scan (k_bins_partial + k_bins_final)
     const bool lookback = L.n_scan_chunks <= 2048;
     const size_t count_bytes = sizeof(int32_t) * (size_t)(L.nb + 1) * L.kc;
     if (!clean || !lookback) {
         hipError_t e = hipMemsetAsync(L.counts, 0, clean ? count_bytes : L.zero_bytes, st);
-        if (e != hipSuccess) return nmf_fail((int)e, "nmf_vm_bin_plan: memset");
+        if (e != hipSuccess) return nmf_fail((int)e, "nmf_vm_query_bwd_segments: memset");
     }
     NMF_LAUNCH(k_plan_hist, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, st, *p, sg, M, L.nbx, L.kc, L.counts, L.keyrank);
     if (lookback) {
@@ -1855,118 +1787,81 @@ int launch_plan(const nmf_vm_params* p, const Segs& sg, int64_t M, const PlanLay
                            L.cursor, L.item_size, L.items, L.n_items);
         if (clean) {         // (grids beyond 500^3: the kept counters are handed back zero by a second memset)
             hipError_t e = hipMemsetAsync(L.counts, 0, count_bytes, st);
-            if (e != hipSuccess) return nmf_fail((int)e, "nmf_vm_bin_plan: memset");
+            if (e != hipSuccess) return nmf_fail((int)e, "nmf_vm_query_bwd_segments: memset");
         }
     }
-    if (place)
-        NMF_LAUNCH(k_plan_place, dim3((unsigned)cdiv(M, 256)), dim3(256), 0, st, sg, M, L.keyrank, L.cursor, L.slot, L.rec0);
-    NMF_CHECK_LAUNCH("nmf_vm_bin_plan");
+    NMF_CHECK_LAUNCH("nmf_vm_query_bwd_segments");
     return NMF_OK;
 }
+int64_t plan_bytes(int64_t M, int32_t grid) { return plan_layout(nullptr, M < 0 ? 0 : M, grid).bytes; }
+int64_t walk_bytes(int64_t M) { return walk_layout(nullptr, M < 0 ? 0 : M).bytes; }
 }  // namespace
 
-extern "C" int64_t nmf_vm_bin_plan_bytes(int64_t M, int32_t grid) {
-    return plan_layout(nullptr, M < 0 ? 0 : M, grid).bytes;
-}
+extern "C" int64_t nmf_vm_bwd_workspace_bytes(int64_t M, int32_t grid) { return plan_bytes(M, grid) + walk_bytes(M); }
 
-extern "C" int64_t nmf_vm_walk_workspace_bytes(int64_t M) { return walk_layout(nullptr, M < 0 ? 0 : M).bytes; }
+extern "C" int64_t nmf_vm_bwd_clean_bytes(int32_t grid) { return clean_layout(nullptr, grid).bytes; }
 
-extern "C" int64_t nmf_vm_bwd_workspace_bytes(int64_t M, int32_t grid) {
-    return nmf_vm_bin_plan_bytes(M, grid) + nmf_vm_walk_workspace_bytes(M);
-}
-
-extern "C" int nmf_vm_bin_plan(const nmf_vm_params* p, const float* const* xyzt, const int64_t* Ms, int32_t n_segs,
-                               void* plan, int64_t plan_bytes, void* stream) {
-    NMF_REQUIRE(p && n_segs >= 0 && n_segs <= MAX_SEG && ((xyzt && Ms) || n_segs == 0), NMF_EINVAL,
-                "nmf_vm_bin_plan: params / segment count (at most NMF_VM_MAX_SEGMENTS)");
-    nmf_vm_bwd_segment segs[MAX_SEG];
-    memset(segs, 0, sizeof(segs));
-    for (int i = 0; i < n_segs; ++i) { segs[i].xyzt = xyzt[i]; segs[i].M = Ms[i]; }
-    Segs sg;
-    int n;
-    const int64_t M = gather_segments(segs, n_segs, sg, n);
-    NMF_REQUIRE(M >= 0, NMF_EINVAL, "nmf_vm_bin_plan: M < 0 or xyzt null");
-    if (M == 0) return NMF_OK;
-    NMF_REQUIRE(M < (1ll << 31), NMF_ERANGE, "nmf_vm_bin_plan: M >= 2^31");
-    NMF_REQUIRE(plan && plan_bytes >= nmf_vm_bin_plan_bytes(M, p->grid), NMF_EINVAL,
-                "nmf_vm_bin_plan: plan buffer too small (see nmf_vm_bin_plan_bytes)");
-    return launch_plan(p, sg, M, plan_layout(plan, M, p->grid), (hipStream_t)stream, true);
-}
-
-static int vm_bwd_impl(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs, int32_t n_segs, const float* const dpk[3],
-                       const float* const dlk[3], const float* const app_planes[3], const float* const app_lines[3],
-                       const float* basis, float* const g_dpk[3], float* const g_dlk[3], float* const g_app_planes[3],
-                       float* const g_app_lines[3], float* g_basis, const void* plan, int64_t plan_bytes, void* workspace,
-                       int64_t workspace_bytes, void* stream, void* clean = nullptr, int64_t clean_bytes = 0) {
+extern "C" int nmf_vm_query_bwd_segments(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs, int32_t n_segs,
+                                         const float* const dpk[3], const float* const dlk[3],
+                                         const float* const app_planes[3], const float* const app_lines[3],
+                                         const float* basis, float* const g_dpk[3], float* const g_dlk[3],
+                                         float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
+                                         void* clean, int64_t clean_bytes, void* workspace, int64_t workspace_bytes,
+                                         void* stream) {
     NMF_REQUIRE(p && n_segs >= 0 && n_segs <= MAX_SEG && (segs || n_segs == 0), NMF_EINVAL,
-                "nmf_vm_query_bwd: params / segment count (at most NMF_VM_MAX_SEGMENTS)");
-    NMF_REQUIRE(!clean || (!plan && clean_bytes >= clean_layout(nullptr, p->grid).bytes && ((uintptr_t)clean & 15) == 0), NMF_EINVAL,
-                "nmf_vm_query_bwd_segments_clean: scratch too small (nmf_vm_bwd_clean_bytes) or not 16-byte aligned");
+                "nmf_vm_query_bwd_segments: params / segment count (at most NMF_VM_MAX_SEGMENTS)");
+    NMF_REQUIRE(!clean || (clean_bytes >= clean_layout(nullptr, p->grid).bytes && ((uintptr_t)clean & 15) == 0), NMF_EINVAL,
+                "nmf_vm_query_bwd_segments: clean scratch too small (nmf_vm_bwd_clean_bytes) or not 16-byte aligned");
     Segs sg;
     int n;
     const int64_t M = gather_segments(segs, n_segs, sg, n);
-    NMF_REQUIRE(M >= 0, NMF_EINVAL, "nmf_vm_query_bwd: M < 0 or xyzt null");
+    NMF_REQUIRE(M >= 0, NMF_EINVAL, "nmf_vm_query_bwd_segments: M < 0 or xyzt null");
     if (M == 0) return NMF_OK;
-    NMF_REQUIRE(M < (1ll << 31), NMF_ERANGE, "nmf_vm_query_bwd: M >= 2^31");
+    NMF_REQUIRE(M < (1ll << 31), NMF_ERANGE, "nmf_vm_query_bwd_segments: M >= 2^31");
     for (int i = 1; i < n; ++i)                              // the kernels branch on segment 0's adjoint set
         NMF_REQUIRE(!sg.d_sigma[i] == !sg.d_sigma[0] && !sg.d_normal[i] == !sg.d_normal[0] && !sg.d_app[i] == !sg.d_app[0],
-                    NMF_EINVAL, "nmf_vm_query_bwd: segments must provide the same adjoints");
+                    NMF_EINVAL, "nmf_vm_query_bwd_segments: segments must provide the same adjoints");
     const float *d_sigma = sg.d_sigma[0], *d_normal = sg.d_normal[0], *d_app = sg.d_app[0];
     bool any_dsf = false;
     for (int i = 0; i < n; ++i) {
         any_dsf = any_dsf || sg.d_sigma_feat[i];
-        NMF_REQUIRE(!d_sigma || sg.sigma_feat[i], NMF_EINVAL, "nmf_vm_query_bwd: d_sigma needs saved sigma_feat");
-        NMF_REQUIRE(!d_normal || sg.grad[i], NMF_EINVAL, "nmf_vm_query_bwd: d_normal needs saved grad");
+        NMF_REQUIRE(!d_sigma || sg.sigma_feat[i], NMF_EINVAL, "nmf_vm_query_bwd_segments: d_sigma needs saved sigma_feat");
+        NMF_REQUIRE(!d_normal || sg.grad[i], NMF_EINVAL, "nmf_vm_query_bwd_segments: d_normal needs saved grad");
     }
     const bool want_d = d_sigma || any_dsf || d_normal;
     const bool want_a = d_app != nullptr;
     NMF_REQUIRE(!want_d || (all3(dpk) && all3(dlk) && all3m(g_dpk) && all3m(g_dlk)), NMF_EINVAL,
-                "nmf_vm_query_bwd: density tables missing");
+                "nmf_vm_query_bwd_segments: density tables missing");
     NMF_REQUIRE(!want_a || (all3(app_planes) && all3(app_lines) && basis && all3m(g_app_planes) && all3m(g_app_lines)),
-                NMF_EINVAL, "nmf_vm_query_bwd: appearance tables missing");
+                NMF_EINVAL, "nmf_vm_query_bwd_segments: appearance tables missing");
     if (!want_d && !want_a) return NMF_OK;
     hipStream_t st = (hipStream_t)stream;
-    PlanLayout L;
-    void* walk_ws = workspace;
-    int64_t walk_bytes = workspace_bytes;
-    if (plan) {          // the sort was done when the positions became known (nmf_vm_bin_plan over the same segment sizes)
-        NMF_REQUIRE(plan_bytes >= nmf_vm_bin_plan_bytes(M, p->grid), NMF_EINVAL, "nmf_vm_query_bwd_planned: plan buffer too small");
-        L = plan_layout(const_cast<void*>(plan), M, p->grid);
-    } else {             // sort here: the plan lives at the front of the workspace
-        NMF_REQUIRE(workspace && workspace_bytes >= nmf_vm_bwd_workspace_bytes(M, p->grid), NMF_EINVAL,
-                    "nmf_vm_query_bwd: workspace too small (see nmf_vm_bwd_workspace_bytes)");
-        L = plan_layout(workspace, M, p->grid);
-        if (clean) {
-            const CleanLayout C = clean_layout(clean, p->grid);
-            L.counts = C.counts;
-            L.scan_state = C.scan_state;
-        }
-        const int rc = launch_plan(p, sg, M, L, st, false, clean != nullptr);
-        if (rc != NMF_OK) return rc;
-        walk_ws = (char*)workspace + L.bytes;
-        walk_bytes = workspace_bytes - L.bytes;
+    NMF_REQUIRE(workspace && workspace_bytes >= nmf_vm_bwd_workspace_bytes(M, p->grid), NMF_EINVAL,
+                "nmf_vm_query_bwd_segments: workspace too small (see nmf_vm_bwd_workspace_bytes)");
+    PlanLayout L = plan_layout(workspace, M, p->grid);      // the sort lives at the front of the workspace
+    if (clean) {
+        const CleanLayout C = clean_layout(clean, p->grid);
+        L.counts = C.counts;
+        L.scan_state = C.scan_state;
     }
-    NMF_REQUIRE(walk_ws && walk_bytes >= nmf_vm_walk_workspace_bytes(M), NMF_EINVAL,
-                "nmf_vm_query_bwd: workspace too small (see nmf_vm_walk_workspace_bytes)");
-    WalkLayout W = walk_layout(walk_ws, M);
+    const int rc = launch_plan(p, sg, M, L, st, clean != nullptr);
+    if (rc != NMF_OK) return rc;
+    WalkLayout W = walk_layout((char*)workspace + L.bytes, M);
     const bool use_copies = want_a && g_basis;
     if (use_copies && clean) W.basis_copies = clean_layout(clean, p->grid).basis_copies;       // (zero: no memset)
     else if (use_copies) {
         hipError_t e = hipMemsetAsync(W.basis_copies, 0, sizeof(float) * BASIS_COPIES * AD * 3 * CA, st);
-        if (e != hipSuccess) return nmf_fail((int)e, "nmf_vm_query_bwd: memset");
+        if (e != hipSuccess) return nmf_fail((int)e, "nmf_vm_query_bwd_segments: memset");
     }
     // the chunk words of the look-back scan are cleared by the launch behind it
     unsigned long long* st_clear = (clean && L.n_scan_chunks <= 2048) ? L.scan_state : nullptr;
     const int n_state = L.n_scan_chunks + 1;
     const dim3 per_sample((unsigned)cdiv(M, 256));
     if (want_a) {
-        if (plan) NMF_LAUNCH(k_brick_records<true>, per_sample, dim3(256), 0, st, *p, sg, L.slot, M, W.rec1, W.d_app_sorted);
-        else NMF_LAUNCH(k_place_records<true>, per_sample, dim3(256), 0, st, *p, sg, M, L.keyrank, L.cursor, L.rec0, W.rec1, W.d_app_sorted, st_clear, n_state);
+        NMF_LAUNCH(k_place_records<true>, per_sample, dim3(256), 0, st, *p, sg, M, L.keyrank, L.cursor, L.rec0, W.rec1, W.d_app_sorted, st_clear, n_state);
         NMF_LAUNCH(k_dcoef, dim3((unsigned)cdiv(M * (3 * CA / 4), 256)), dim3(256), 0, st, W.d_app_sorted, basis, M,
                            W.dcoef);
-    } else if (plan)
-        NMF_LAUNCH(k_brick_records<false>, per_sample, dim3(256), 0, st, *p, sg, L.slot, M, W.rec1, W.d_app_sorted);
-    else
+    } else
         NMF_LAUNCH(k_place_records<false>, per_sample, dim3(256), 0, st, *p, sg, M, L.keyrank, L.cursor, L.rec0, W.rec1, W.d_app_sorted, st_clear, n_state);
     const int nz = (want_d ? 1 : 0) + (want_a ? 1 : 0);
     const int z_density = want_d ? 0 : -1, z_app = want_a ? (want_d ? 1 : 0) : -1;
@@ -1990,58 +1885,6 @@ static int vm_bwd_impl(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs, i
 #undef NMF_LAUNCH_BWD_KERNEL
     if (use_copies)
         NMF_LAUNCH(k_basis_reduce, dim3((unsigned)cdiv(AD * 3 * CA, 256)), dim3(256), 0, st, W.basis_copies, g_basis, clean ? 1 : 0);
-    NMF_CHECK_LAUNCH("nmf_vm_query_bwd");
+    NMF_CHECK_LAUNCH("nmf_vm_query_bwd_segments");
     return NMF_OK;
-}
-
-extern "C" int64_t nmf_vm_bwd_clean_bytes(int32_t grid) { return clean_layout(nullptr, grid).bytes; }
-
-extern "C" int nmf_vm_query_bwd_segments_clean(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs, int32_t n_segs,
-                                               const float* const dpk[3], const float* const dlk[3],
-                                               const float* const app_planes[3], const float* const app_lines[3],
-                                               const float* basis, float* const g_dpk[3], float* const g_dlk[3],
-                                               float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                                               void* clean, int64_t clean_bytes, void* workspace, int64_t workspace_bytes,
-                                               void* stream) {
-    NMF_REQUIRE(clean, NMF_EINVAL, "nmf_vm_query_bwd_segments_clean: scratch null");
-    return vm_bwd_impl(p, segs, n_segs, dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis,
-                       nullptr, 0, workspace, workspace_bytes, stream, clean, clean_bytes);
-}
-
-extern "C" int nmf_vm_query_bwd_segments(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs, int32_t n_segs,
-                                         const float* const dpk[3], const float* const dlk[3],
-                                         const float* const app_planes[3], const float* const app_lines[3],
-                                         const float* basis, float* const g_dpk[3], float* const g_dlk[3],
-                                         float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                                         void* workspace, int64_t workspace_bytes, void* stream) {
-    return vm_bwd_impl(p, segs, n_segs, dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis,
-                       nullptr, 0, workspace, workspace_bytes, stream);
-}
-
-extern "C" int nmf_vm_query_bwd_planned(const nmf_vm_params* p, const nmf_vm_bwd_segment* segs, int32_t n_segs,
-                                        const float* const dpk[3], const float* const dlk[3],
-                                        const float* const app_planes[3], const float* const app_lines[3],
-                                        const float* basis, float* const g_dpk[3], float* const g_dlk[3],
-                                        float* const g_app_planes[3], float* const g_app_lines[3], float* g_basis,
-                                        const void* plan, int64_t plan_bytes, void* workspace, int64_t workspace_bytes,
-                                        void* stream) {
-    NMF_REQUIRE(plan, NMF_EINVAL, "nmf_vm_query_bwd_planned: plan null");
-    return vm_bwd_impl(p, segs, n_segs, dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis,
-                       plan, plan_bytes, workspace, workspace_bytes, stream);
-}
-
-extern "C" int nmf_vm_query_bwd(const nmf_vm_params* p, const float* xyzt, int64_t M, const float* const dpk[3],
-                                const float* const dlk[3], const float* const app_planes[3],
-                                const float* const app_lines[3], const float* basis, const float* sigma_feat,
-                                const float* grad, const float* d_sigma, const float* d_sigma_feat,
-                                const float* d_normal, const float* d_app, float* const g_dpk[3],
-                                float* const g_dlk[3], float* const g_app_planes[3], float* const g_app_lines[3],
-                                float* g_basis, void* workspace, int64_t workspace_bytes, void* stream) {
-    NMF_REQUIRE(p && M >= 0, NMF_EINVAL, "nmf_vm_query_bwd: params");
-    if (M == 0) return NMF_OK;
-    nmf_vm_bwd_segment seg;
-    seg.xyzt = xyzt; seg.M = M; seg.sigma_feat = sigma_feat; seg.grad = grad; seg.d_sigma = d_sigma;
-    seg.d_sigma_feat = d_sigma_feat; seg.d_normal = d_normal; seg.d_app = d_app;
-    return nmf_vm_query_bwd_segments(p, &seg, 1, dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes,
-                                     g_app_lines, g_basis, workspace, workspace_bytes, stream);
 }

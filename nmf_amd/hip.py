@@ -81,17 +81,17 @@ class CopySlot(C.Structure):
 
 EXPORTS = [
     "nmf_version", "nmf_last_error_string", "nmf_event_create", "nmf_event_create_timed", "nmf_event_elapsed_ms", "nmf_event_destroy", "nmf_event_record", "nmf_event_synchronize",
-    "nmf_stream_wait_event", "nmf_memcpy_d2h_async", "nmf_host_alloc_mapped", "nmf_host_free_mapped", "nmf_publish_i64x2", "nmf_wait_seq", "nmf_set_launch_probe", "nmf_alpha_pack", "nmf_march_count", "nmf_march_scan", "nmf_march_scan_workspace_bytes", "nmf_march_scan_publish", "nmf_bounce_index_publish", "nmf_bounce_index_live", "nmf_vm_query_fwd_live",
-    "nmf_march_fill", "nmf_march_dense", "nmf_vm_pack_density", "nmf_vm_query_fwd", "nmf_vm_query_fwd_bf16", "nmf_vm_query_rows", "nmf_vm_query_sigma", "nmf_sat_lookup_bwd_dirs", "nmf_vm_query_bwd",
+    "nmf_stream_wait_event", "nmf_host_alloc_mapped", "nmf_host_free_mapped", "nmf_publish_i64x2", "nmf_wait_seq", "nmf_set_launch_probe", "nmf_alpha_pack", "nmf_march_count", "nmf_march_scan", "nmf_march_scan_workspace_bytes",
+    "nmf_march_fill", "nmf_march_dense", "nmf_vm_pack_density", "nmf_vm_query_fwd", "nmf_vm_query_rows", "nmf_vm_query_sigma", "nmf_sat_lookup_bwd_dirs",
     "nmf_vm_unpack_density_grad", "nmf_vm_bwd_workspace_bytes", "nmf_composite_fwd", "nmf_composite_bwd", "nmf_segment_sum",
     "nmf_sat_build", "nmf_sat_build_bwd", "nmf_sat_lookup_fwd", "nmf_sat_lookup_bwd", "nmf_sat_lookup_bwd_binned",
     "nmf_sat_lookup_bwd_workspace_bytes",
     "nmf_select_bounces", "nmf_select_total", "nmf_view_adjoint_to_rays", "nmf_expand_segments", "nmf_segment_sum_wide",
-    "nmf_brdf_mlp_fwd", "nmf_brdf_mlp_bwd", "nmf_brdf_mlp_bwd_workspace_bytes", "nmf_brdf_mlp_image_bytes", "nmf_brdf_mlp_pack",
-    "nmf_brdf_mlp_fwd_packed", "nmf_brdf_mlp_bwd_packed", "nmf_brdf_mlp_bwd_segments", "nmf_brdf_mlp_bwd_segments_workspace_bytes", "nmf_heads_fwd", "nmf_heads_bwd", "nmf_ggx_rays_fwd", "nmf_ggx_rays_bwd", "nmf_ggx_rays_bwd_view", "nmf_ggx_prob", "nmf_shade_mix_fwd", "nmf_shade_mix_bwd", "nmf_shade_mix_bwd_view",
-    "nmf_adam_step", "nmf_adam_step_guarded", "nmf_bounce_index", "nmf_bounce_index_workspace_bytes", "nmf_bounce_prep_fwd", "nmf_bounce_prep_bwd",
+    "nmf_brdf_mlp_fwd", "nmf_brdf_mlp_image_bytes", "nmf_brdf_mlp_pack",
+    "nmf_brdf_mlp_bwd_segments", "nmf_brdf_mlp_bwd_segments_workspace_bytes", "nmf_heads_fwd", "nmf_heads_bwd", "nmf_ggx_rays_fwd", "nmf_ggx_rays_bwd", "nmf_ggx_rays_bwd_view", "nmf_ggx_prob", "nmf_shade_mix_fwd", "nmf_shade_mix_bwd", "nmf_shade_mix_bwd_view",
+    "nmf_adam_step", "nmf_bounce_index", "nmf_bounce_index_workspace_bytes", "nmf_bounce_prep_fwd", "nmf_bounce_prep_bwd",
     "nmf_ray_compose_fwd", "nmf_ray_compose_bwd", "nmf_l1_mean_fwd", "nmf_l1_mean_bwd", "nmf_sqerr_fwd", "nmf_sqerr_bwd",
-    "nmf_loss_mix_fwd", "nmf_loss_mix_bwd", "nmf_loss_head", "nmf_loss_head_workspace_bytes", "nmf_bg_adjoint", "nmf_vm_query_bwd_segments", "nmf_vm_query_bwd_segments_clean", "nmf_vm_bwd_clean_bytes", "nmf_vm_unpack_density_grad_l1", "nmf_vm_bin_plan", "nmf_vm_bin_plan_bytes", "nmf_vm_walk_workspace_bytes", "nmf_vm_query_bwd_planned", "nmf_sh_project",
+    "nmf_loss_mix_fwd", "nmf_loss_mix_bwd", "nmf_loss_head", "nmf_loss_head_workspace_bytes", "nmf_bg_adjoint", "nmf_vm_query_bwd_segments", "nmf_vm_bwd_clean_bytes", "nmf_sh_project",
     "nmf_retrace_scores", "nmf_argsort_f32", "nmf_argsort_workspace_bytes", "nmf_topk_select", "nmf_topk_select_workspace_bytes", "nmf_alpha_coarse", "nmf_alpha_coarse_words", "nmf_bounce_index_select", "nmf_bounce_prep_fwd_heads", "nmf_bounce_prep_heads_bwd", "nmf_multi_copy",
     "nmf_ssim", "nmf_ssim_workspace_bytes", "nmf_normal_err", "nmf_normal_err_workspace_bytes",
     "nmf_material_maps",
@@ -168,15 +168,6 @@ def _p(t, dtype=None):
     if not t.is_contiguous():
         raise NmfHipError("tensor must be contiguous")
     return t.data_ptr() or None
-
-
-def _p3(ts, dtype=torch.float32):
-    arr = (C.c_void_p * 3)()
-    if ts is None:
-        return None
-    for i in range(3):
-        arr[i] = _p(ts[i], dtype)
-    return arr
 
 
 def channels_last_ptr_ok(t):
@@ -372,31 +363,7 @@ def to_bf16_tables(srcs, dsts=None):
     return dsts
 
 
-def vm_query_bwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, sigma_feat, grad, d_sigma, d_sigma_feat,
-                 d_normal, d_app, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis=None):
-    M = xyzt.shape[0]
-    want_d = d_sigma is not None or d_sigma_feat is not None or d_normal is not None
-    want_a = d_app is not None
-    nbytes = _lib.nmf_vm_bwd_workspace_bytes(C.c_int64(M), C.c_int32(p.grid))
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=xyzt.device)
-    _check(_lib.nmf_vm_query_bwd(C.byref(p), _p(xyzt, torch.float32), C.c_int64(M),
-                                 _p3(dpk) if want_d else None, _p3(dlk) if want_d else None,
-                                 _p3(app_planes) if want_a else None, _p3(app_lines) if want_a else None,
-                                 _p(basis) if want_a else None, _p(sigma_feat), _p(grad), _p(d_sigma),
-                                 _p(d_sigma_feat), _p(d_normal), _p(d_app),
-                                 _p3(g_dpk) if want_d else None, _p3(g_dlk) if want_d else None,
-                                 _p3(g_app_planes) if want_a else None, _p3(g_app_lines) if want_a else None,
-                                 _p(g_basis if want_a else None), _p(ws), C.c_int64(nbytes), _stream()), "nmf_vm_query_bwd")
-
-
 VM_MAX_SEGMENTS = 4
-
-
-def vm_bin_plan(p, xyzts):
-    """The brick sort of a backward walk over the sample sets `xyzts` ([M_i,4] each), from the positions alone -> opaque plan
-    tensor for vm_query_bwd_segments(..., plan=) over the same sets in the same order (a training pass builds it under its
-    forward; the backward then only permutes the adjoints)."""
-    return HOST_EXT.vm_bin_plan(C.addressof(p), list(xyzts), _stream())
 
 
 def vm_bwd_clean_scratch(p, device):
@@ -405,16 +372,19 @@ def vm_bwd_clean_scratch(p, device):
 
 
 def vm_query_bwd_segments(p, segs, dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines,
-                          g_basis=None, plan=None, clean=None):
+                          g_basis=None, clean=None):
     """One backward walk over several sample sets (no concatenation).  segs: list of tuples
     (xyzt, sigma_feat, grad, d_sigma, d_sigma_feat, d_normal, d_app) -- the argument order of vm_query_bwd.
-    plan: vm_bin_plan of the same sample sets (the sort is then not redone).  clean: vm_bwd_clean_scratch (no memset launches)."""
-    args = (C.addressof(p), list(segs), dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis)
-    if clean is not None:
-        return HOST_EXT.vm_query_bwd_clean(*args, clean, _stream())
-    if plan is not None:
-        return HOST_EXT.vm_query_bwd_planned(*args, plan, _stream())
-    return HOST_EXT.vm_query_bwd_segments(*args, _stream())
+    clean: vm_bwd_clean_scratch (no memset launches)."""
+    return HOST_EXT.vm_query_bwd_segments(C.addressof(p), list(segs), dpk, dlk, app_planes, app_lines, basis, g_dpk, g_dlk,
+                                          g_app_planes, g_app_lines, g_basis, clean, _stream())
+
+
+def vm_query_bwd(p, xyzt, dpk, dlk, app_planes, app_lines, basis, sigma_feat, grad, d_sigma, d_sigma_feat,
+                 d_normal, d_app, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis=None):
+    """the walk over ONE sample set: vm_query_bwd_segments with a single segment"""
+    return vm_query_bwd_segments(p, [(xyzt, sigma_feat, grad, d_sigma, d_sigma_feat, d_normal, d_app)], dpk, dlk, app_planes,
+                                 app_lines, basis, g_dpk, g_dlk, g_app_planes, g_app_lines, g_basis)
 
 
 def vm_unpack_density_grad(p, g_dpk, g_dlk, out=None, l1=None):

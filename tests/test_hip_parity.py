@@ -189,7 +189,7 @@ def _vm_backward(hip, p, xyz_d, tabs, sf, gr, d_sigma, d_sf, d_normal, d_app, co
     hip.vm_query_bwd(p, xyz_d, dpk, dlk, apl, ali, basis, sf, gr, d_sigma, d_sf, d_normal, d_app, g_dpk, g_dlk,
                      g_apl, g_ali, g_basis)
     gp, gl = hip.vm_unpack_density_grad(p, g_dpk, g_dlk)
-    # the L1 term's gradient in the same launch (nmf_vm_unpack_density_grad_l1) = unpack + nmf_l1_mean_bwd(accumulate), bit for bit
+    # the L1 term's gradient in the same launch (the l1 arguments of nmf_vm_unpack_density_grad) = unpack + nmf_l1_mean_bwd(accumulate), bit for bit
     gq = torch.Generator().manual_seed(3)
     xs = [torch.randn(1, 16, G, G, generator=gq).to(DEV).contiguous(memory_format=torch.channels_last) for _ in range(3)] + \
          [torch.randn(1, 16, G, 1, generator=gq).to(DEV).contiguous(memory_format=torch.channels_last) for _ in range(3)]
@@ -1069,7 +1069,7 @@ def test_vm_appearance_rows_kernel_equals_the_full_query(M):
 
 
 def test_vm_query_bf16_tables():
-    """BASELINE configs[1]: nmf_vm_query_fwd_bf16 reads bfloat16 factor tables (half the bytes per tap) with fp32 arithmetic.
+    """BASELINE configs[1]: nmf_vm_query_fwd with tables_bf16 reads bfloat16 factor tables (half the bytes per tap) with fp32 arithmetic.
     (1) exactly the fp32 kernel's result on tables rounded to bf16; (2) within bf16 resolution of the fp32-table result;
     (3) a training step runs (backward walk on the fp32 master tables) and moves the parameters."""
     hip = _hip()
@@ -1644,7 +1644,7 @@ def test_loss_mix_matches_torch():
 @pytest.mark.parametrize("with_app", [False, True])
 def test_vm_backward_segments_equal_concatenation(with_app):
     """nmf_vm_query_bwd_segments over ragged sample sets (incl. an empty one) accumulates the same table gradients as
-    nmf_vm_query_bwd over their concatenation (tensor_nerf.py:286-393: primary + re-traced samples of one pass)."""
+    hip.vm_query_bwd (one segment) over their concatenation (tensor_nerf.py:286-393: primary + re-traced samples of one pass)."""
     from nmf_amd import hip, synthetic
     G = 32
     cfg = O.Cfg(grid=G)
@@ -1677,18 +1677,49 @@ def test_vm_backward_segments_equal_concatenation(with_app):
     fa, fb = flat(a), flat(b)
     assert fb.abs().max() > 0
     assert_close(fa, fb, rtol=2e-5, atol=2e-5 * float(fb.abs().max()), what="segmented walk vs concatenation")
+    # the one-set convenience wrapper = a walk with that set as its single segment
+    c = bufs()
+    hip.vm_query_bwd_segments(p, [tuple(cat)], dpk, dlk, apl, ali, basis, c[0], c[1], c[2], c[3], c[4] if with_app else None)
+    assert_close(fb, flat(c), rtol=2e-5, atol=2e-5 * float(fb.abs().max()), what="vm_query_bwd vs a one-segment walk")
     with pytest.raises(hip.NmfHipError):                       # mixed adjoint sets are rejected
         bad = [segs[0], (segs[3][0], None, None, None, None, None, None)]
         hip.vm_query_bwd_segments(p, bad, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], None)
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True])
+def test_vm_forward_with_a_device_side_count_equals_the_sized_query(bf16):
+    """nmf_vm_query_fwd with M_live (the sample count read from the device, the launch sized by the buffer's bound) writes the bits
+    of the query sized by M itself into the first M rows, for fp32 and for bfloat16 tables.  3001 and 3501 both end in a partial
+    256-thread block."""
+    import ctypes
+    from nmf_amd import hip, synthetic
+    G, M, CAP = 32, 3001, 3501
+    cfg = O.Cfg(grid=G)
+    sd = synthetic.state_dict_s1(grid=G, bg_resolution=8, seed=4)
+    p, dpk, dlk, apl, ali, basis = _field_tables(hip, sd, cfg)
+    if bf16:
+        dpk, dlk, apl, ali = (hip.to_bf16_tables(list(ts)) for ts in (dpk, dlk, apl, ali))
+    g = torch.Generator().manual_seed(17)
+    buf = torch.cat([(torch.rand(CAP, 3, generator=g) * 2 - 1) * 1.45, torch.zeros(CAP, 1)], 1).to(DEV).contiguous()
+    ref = hip.vm_query_fwd(p, buf[:M].contiguous(), dpk, dlk, apl, ali, basis)
+    count = torch.tensor([M], dtype=torch.int64, device=DEV)
+    got = hip.HOST_EXT.vm_query_fwd(ctypes.addressof(p), buf, dpk, dlk, apl, ali, basis, True, True, True, False, hip._stream(),
+                                    live=count.data_ptr())
+    for name, a, b in zip(("sigma_feat", "sigma", "grad", "normal", "app"), ref, got):
+        assert b.shape[0] == CAP and float(a.abs().max()) > 0
+        assert torch.equal(a, b[:M]), f"{name}: the device-side count must not change the first M rows"
+    with pytest.raises(hip.NmfHipError):                       # all tables of a call share one dtype
+        mixed = [dpk[0], dpk[1], (dpk[2].float() if bf16 else dpk[2].bfloat16())]
+        hip.vm_query_fwd(p, buf[:M].contiguous(), mixed, dlk, apl, ali, basis)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("with_app", [False, True])
 @pytest.mark.parametrize("grid", [32, 57])
-def test_vm_backward_with_a_plan_of_the_forward_equals_the_self_sorting_walk(with_app, grid):
-    """nmf_vm_bin_plan (the brick sort, from the positions alone) + nmf_vm_query_bwd_planned accumulate what
-    nmf_vm_query_bwd_segments does when it sorts by itself (autograd of fields/tensoRF.py:181-205); the plan is reusable
-    (two walks with different adjoints over one plan)."""
+def test_vm_backward_on_a_kept_scratch_equals_the_walk_with_memsets(with_app, grid):
+    """nmf_vm_query_bwd_segments with the counters of its brick sort in a scratch the caller keeps (`clean`) accumulates what it
+    does when it zeroes them itself (autograd of fields/tensoRF.py:181-205), walk after walk, and hands the scratch back zero."""
     from nmf_amd import hip, synthetic
     G = grid
     cfg = O.Cfg(grid=G)
@@ -1724,17 +1755,8 @@ def test_vm_backward_with_a_plan_of_the_forward_equals_the_self_sorting_walk(wit
                 [z(G, 24) for _ in range(3)], z(24, 72))
 
     flat = lambda t: torch.cat([x.reshape(-1) for x in (t[0] + t[1] + t[2] + t[3] + [t[4]])]).cpu()  # noqa: E731
-    plan = hip.vm_bin_plan(p, xyzs)
     impl = hip.vm_query_bwd_segments
-    for seed in (1, 2):
-        segs = make_segs(seed)
-        a, b = bufs(), bufs()
-        impl(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None)
-        impl(p, segs, dpk, dlk, apl, ali, basis, b[0], b[1], b[2], b[3], b[4] if with_app else None, plan=plan)
-        fa, fb = flat(a), flat(b)
-        assert fa.abs().max() > 0
-        assert_close(fb, fa, rtol=2e-5, atol=2e-5 * float(fa.abs().max()), what="planned walk vs self-sorting walk")
-    # the counters of the sort in a scratch the caller keeps (nmf_vm_query_bwd_segments_clean): zero before, zero after, the same
+    # the counters of the sort in a scratch the caller keeps (`clean`): zero before, zero after, the same
     # gradients walk after walk (each walk hands the scratch back zero instead of being preceded by memset launches)
     clean = hip.vm_bwd_clean_scratch(p, DEV)
     assert clean.numel() == hip._lib.nmf_vm_bwd_clean_bytes(G) and int(clean.count_nonzero()) == 0
@@ -1744,16 +1766,12 @@ def test_vm_backward_with_a_plan_of_the_forward_equals_the_self_sorting_walk(wit
         impl(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None)
         impl(p, segs, dpk, dlk, apl, ali, basis, b[0], b[1], b[2], b[3], b[4] if with_app else None, clean=clean)
         fa, fb = flat(a), flat(b)
+        assert fa.abs().max() > 0
         assert_close(fb, fa, rtol=2e-5, atol=2e-5 * float(fa.abs().max()), what="walk on a kept scratch vs walk with memsets")
         assert int(clean.count_nonzero()) == 0, "the scratch must come back zero"
     with pytest.raises(hip.NmfHipError):                       # a scratch that is too small is refused
         hip.vm_query_bwd_segments(p, make_segs(1), dpk, dlk, apl, ali, basis, *bufs()[:4], bufs()[4] if with_app else None,
                                   clean=torch.zeros(64, dtype=torch.uint8, device=DEV))
-    with pytest.raises(hip.NmfHipError):                       # a plan of fewer samples than the walk is refused
-        small = hip.vm_bin_plan(p, [xyzs[2]])
-        segs = make_segs(1)
-        a = bufs()
-        hip.vm_query_bwd_segments(p, segs, dpk, dlk, apl, ali, basis, a[0], a[1], a[2], a[3], a[4] if with_app else None, plan=small)
 
 
 @pytest.mark.gpu
@@ -1850,7 +1868,8 @@ def test_host_extension_wrappers_vs_cpu_references():
     with pytest.raises(hip.NmfHipError):
         hip.brdf_mlp_bwd_segments([mlp_w[0].cpu()] + mlp_w[1:], [mlp_set], [torch.zeros_like(t) for t in mlp_w])
     with pytest.raises(hip.NmfHipError):
-        hip.vm_bin_plan(tabs[0], [xyz_c])
+        hip.vm_query_bwd_segments(tabs[0], [(xyz_c, sf, gr, torch.ones_like(sf), None, None, None)], *tabs[1:],
+                                  *[[torch.zeros_like(t) for t in ts] for ts in tabs[1:5]])
 
 
 def _same_bits(a, b):
