@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 123
+#define NMF_ABI_VERSION 124
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -761,6 +761,35 @@ int nmf_relight_ratio(const float* pred, const float* gt, int64_t n_img, int64_t
 int64_t nmf_relight_adjust_workspace_bytes(int64_t n_img, int64_t H, int64_t W);
 int nmf_relight_adjust(const float* pred, const float* gt, float multi_r, float multi_g, float multi_b, int64_t n_img, int64_t H,
                        int64_t W, float* tp, float* tg, double* sqerr, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Camera paths: the two per-frame kernels around the evaluation pass (nmf_amd/renderer.py:evaluation_path).
+ *
+ * nmf_camera_rays: the pixel rays of a pinhole camera from its camera-to-world matrix (row-major 3x4: rotation r00..r22, translation
+ *   tx ty tz; OpenCV axes, x right, y down, z forward), as the loader builds them on the host for every view of a data set
+ *   (dataLoader/ray_utils.py:23-41, 65-85; dataLoader/blender.py:97-122).  rays [H W][6] = origin | unit direction, pixel
+ *   p = row W + col.  fp32, one rounding per operation, in this order:
+ *     x = ((col + 0.5) - cx) / fx,  y = ((row + 0.5) - cy) / fy,  n = sqrt((x x + y y) + 1),  d = (x / n, y / n, 1 / n),
+ *     world_i = (r_i0 d_x + r_i1 d_y) + r_i2 d_z,  origin = (tx, ty, tz).
+ *   fx != fy and an off-centre principal point are allowed.  One launch, one lane per pixel; two runs give the same bytes.  Refused
+ *   (nothing launched): a null or not 8-byte aligned rays, H or W below 1, fx or fy zero or not finite, a pose, cx or cy that is not
+ *   finite (NMF_EINVAL); H W above 2^31 - 1 (NMF_ERANGE).
+ *
+ * nmf_frame_finish: the float maps of one frame -> one 8-bit picture ready to encode.  Each non-null input is one panel, side by side
+ *   in the order rgb [P][3] | depth [P] | normal [P][3] | acc [P], P = H W: panel k of pixel (row, col) is the three bytes at
+ *   out[((row n_panels + k) W + col) 3].  Per value, a NaN counts as 0 before anything else; the casts truncate:
+ *     rgb     (uint8)(clamp(v, 0, 1) * 255)                                         (renderer.py:343-347, after a clip to [0, 1])
+ *     depth   q = (uint8)(255 clamp((v - near) / ((far - near) + 1e-8f), 0, 1)); the pixel is lut[q] (lut [256][3] bytes), or
+ *             (q, q, q) when lut is NULL          (utils.visualize_depth_numpy with minmax = near_far, clamped instead of wrapped)
+ *     normal  (uint8)clamp(v * 127 + 128, 0, 255)                                   (renderer.py:440-451, vis_world_normal)
+ *     acc     (uint8)(255 clamp(v, 0, 1)), grey
+ *   One launch; a lane owns four consecutive output pixels and stores three dwords when out is 4-byte aligned, bytes otherwise and in
+ *   the tail.  Refused (nothing launched): all four inputs null, a null out, H or W below 1, near or far not finite, far <= near
+ *   (NMF_EINVAL); H W n_panels above 2^31 - 1 (NMF_ERANGE). */
+int nmf_camera_rays(float r00, float r01, float r02, float r10, float r11, float r12, float r20, float r21, float r22, float tx,
+                    float ty, float tz, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float* rays, void* stream);
+int nmf_frame_finish(const float* rgb, const float* depth, const float* normal, const float* acc, float near, float far,
+                     const uint8_t* lut, int32_t H, int32_t W, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,16 @@ class BlenderDataset(torch.utils.data.Dataset):
             self.all_rays = torch.stack(self.all_rays, 0)
             self.all_rgbs = torch.stack(self.all_rgbs, 0).reshape(-1, *self.img_wh[::-1], c)[..., :3]
 
+    @property
+    def render_path(self):
+        """the camera path `render_path=True` renders (train.py:884-901): 120 poses [120, 4, 4] float32 on the circle at the mean
+        distance and elevation of this split's cameras (nmf_amd.camera_path.from_dataset(self, "orbit", 120)), built on first use.
+        The reference's Blender loader has no render_path, so its own render_path=True raises on a Blender scene."""
+        if getattr(self, "_render_path", None) is None:
+            from nmf_amd.camera_path import from_dataset
+            self._render_path = from_dataset(self, "orbit", 120)
+        return self._render_path
+
     def world2ndc(self, points, lindisp=None):
         return (points - self.center.to(points.device)) / self.radius.to(points.device)
 

@@ -100,6 +100,7 @@ EXPORTS = [
     "nmf_env_resample",
     "nmf_relight_frame", "nmf_relight_ratio", "nmf_relight_ratio_workspace_bytes", "nmf_relight_adjust",
     "nmf_relight_adjust_workspace_bytes",
+    "nmf_camera_rays", "nmf_frame_finish",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -1064,3 +1065,82 @@ def marching_cubes(vol, level):
     if V > MC_INDEX_MAX or 3 * F > MC_INDEX_MAX:
         raise NmfHipError(f"marching cubes: {V} vertices / {F} faces do not fit int32 face indices (V and 3 F at most 2^31 - 1)")
     return mc_emit(vol, level, cases, vcount, tcount, V, F)
+
+
+# ---- camera paths: rays from a pose, the finished 8-bit frame (csrc/camera.hip; renderer.evaluation_path) ----------------------------
+def depth_colour_table():
+    """the default colour table of the depth panel, uint8 [256, 3] (host): the analytic "jet" in float64, s = q / 255,
+    r, g, b = clip(1.5 - |4 s - 3|, |4 s - 2|, |4 s - 1|, 0, 1), byte = floor(255 c + 0.5).  The reference maps depth through OpenCV's
+    COLORMAP_JET table (utils.visualize_depth_numpy), which differs from the formula by a few levels"""
+    s = np.arange(256, dtype=np.float64) / 255.0
+    c = np.stack([np.clip(1.5 - np.abs(4.0 * s - k), 0.0, 1.0) for k in (3.0, 2.0, 1.0)], -1)
+    return np.floor(255.0 * c + 0.5).astype(np.uint8)
+
+
+_depth_lut = {}
+
+
+def _device_lut(device):
+    key = str(device)
+    if key not in _depth_lut:
+        _depth_lut[key] = torch.from_numpy(depth_colour_table()).to(device)
+    return _depth_lut[key]
+
+
+def camera_rays(c2w, fx, fy, cx, cy, H, W, device="cuda", out=None):
+    """nmf_camera_rays: the [H W, 6] rays (origin | unit direction) of the pinhole camera with camera-to-world matrix c2w (host values,
+    [3, 4] or [4, 4], OpenCV axes as BlenderDataset.poses) -- the loader's construction (pixel centres at +0.5, directions @ R^T) on the
+    device.  out: an fp32 device tensor of 6 H W elements to fill (one buffer for a whole path); default: a new one on `device`."""
+    H, W = int(H), int(W)
+    if out is None:
+        if torch.device(device).type != "cuda":
+            raise NmfHipError("camera_rays: nmf_amd operators need device tensors (no CPU path)")
+        if H < 1 or W < 1:
+            raise NmfHipError(f"camera_rays: H and W are at least 1, got {H} x {W}")
+        out = torch.empty((H * W, 6), dtype=torch.float32, device=device)
+    ptr = _p(out, torch.float32)
+    if out.numel() != 6 * H * W:
+        raise NmfHipError(f"camera_rays: out holds {out.numel()} values, {H} x {W} pixels need {6 * H * W}")
+    m = np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise NmfHipError(f"camera_rays: c2w is [3, 4] or [4, 4], got {m.shape}")
+    pose = [float(v) for v in m[:3, :3].reshape(-1)] + [float(v) for v in m[:3, 3]]
+    with torch.cuda.device(out.device):
+        _check(_lib.nmf_camera_rays(*pose, float(fx), float(fy), float(cx), float(cy), H, W, ptr, _stream()), "nmf_camera_rays")
+    return out.view(H * W, 6)
+
+
+def frame_finish(H, W, rgb=None, depth=None, normal=None, acc=None, near_far=(0.0, 1.0), lut="jet", out=None):
+    """nmf_frame_finish: the float maps of one frame (each an fp32 device tensor of H W pixels, or None) -> uint8 [H, n_panels W, 3], the
+    panels side by side in the order rgb | depth | normal | acc with the reference's 8-bit conversions (include/nmf_hip.h).  lut: "jet"
+    (depth_colour_table, cached per device), None (grey depth) or a uint8 [256, 3] device tensor.  out: the strip to fill."""
+    H, W = int(H), int(W)
+    maps = (("rgb", rgb, 3), ("depth", depth, 1), ("normal", normal, 3), ("acc", acc, 1))
+    given = [t for _, t, _ in maps if t is not None]
+    if not given:
+        raise NmfHipError("frame_finish: no panel (rgb, depth, normal and acc are all None)")
+    ptrs = []
+    for name, t, c in maps:
+        if t is not None:
+            if not t.is_cuda:
+                raise NmfHipError(f"frame_finish: {name} must be a device tensor (no CPU path)")
+            if t.device != given[0].device:
+                raise NmfHipError(f"frame_finish: {name} is on another device")
+            if t.numel() != c * H * W:
+                raise NmfHipError(f"frame_finish: {name} holds {t.numel()} values, {H} x {W} pixels need {c * H * W}")
+        ptrs.append(_p(t, torch.float32))
+    dev, n = given[0].device, len(given)
+    if isinstance(lut, str):
+        if lut != "jet":
+            raise NmfHipError(f"frame_finish: unknown colour table '{lut}'")
+        lut = _device_lut(dev) if depth is not None else None
+    if lut is not None and (lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or lut.device != dev):
+        raise NmfHipError("frame_finish: lut is a uint8 [256, 3] tensor on the maps' device")
+    if out is None:
+        out = torch.empty((H, n * W, 3), dtype=torch.uint8, device=dev)
+    if out.numel() != 3 * n * H * W or out.device != dev:
+        raise NmfHipError(f"frame_finish: out holds {out.numel()} bytes on {out.device}, {n} panels of {H} x {W} need {3 * n * H * W}")
+    with torch.cuda.device(dev):
+        _check(_lib.nmf_frame_finish(*ptrs, float(near_far[0]), float(near_far[1]), _p(lut, torch.uint8), H, W, _p(out, torch.uint8),
+                                     _stream()), "nmf_frame_finish")
+    return out.view(H, n * W, 3)

@@ -28,6 +28,16 @@ the line gains light_frames and, per frame, the seconds of the environment updat
 --relight-eval DIR (nmf_amd/relight_eval.py; the reference's scripts/relighting_calc.ipynb) scores the relit test views
 of an EXR set against its ground truth: HDR frames {idx:03d}.exr, adjusted/{idx:03d}.png and stats.yaml go to DIR, and the line gains
 relight = {psnr, ssim, multiplier, views}.  Combines with --env-rotate, --bg-res and --n-vis.
+
+    python -m nmf_amd.render --ckpt log/lego.th --datadir /data/nerf_synthetic/lego --path orbit --frames 120 --out imgs/
+    python -m nmf_amd.render --ckpt log/s1.th --fixed-bg studio.exr --env-rotate 90 0 0 --path spiral --panels rgb,depth,normal --out imgs/
+    python -m nmf_amd.render --ckpt log/s1.th --path imgs/path/transforms_path.json --out again/
+
+--path orbit|spiral|interp|FILE.json (nmf_amd/camera_path.py, renderer.evaluation_path; the reference's render_path,
+train.py:884-901) renders views that are in no data set into OUT/path/: --frames poses around the data set's scene (without
+--datadir: a --res square camera, radius 4, elevation 30 degrees) or the poses of a transforms file; {k:03d}.png, depth/,
+world_normal/, acc_map/ per --panels, video.png / depthvideo.png (animated PNGs at --fps; --animation gif|none) and
+transforms_path.json.  Rays and 8-bit frames are made on the device; PNGs are encoded on a writer thread.  The line gains `path`.
 """
 import argparse
 import json
@@ -102,6 +112,37 @@ def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None):
     return dict(light_frames=n, light_env_seconds=env_s, light_render_seconds=render_s)
 
 
+def render_path(nerf, args, ds, near_far, panels, noise, dev):
+    """--path: the poses (nmf_amd/camera_path.py) and the camera, rendered by renderer.evaluation_path into <out>/path/ under the
+    lighting the command set up (--fixed-bg, --env-rotate, --bg-res).  Without a data set the camera is --res square with the
+    synthetic scene's camera_angle_x and the orbit has radius 4 at elevation 30 degrees around the origin.  -> the `path` key"""
+    import math
+
+    from . import camera_path
+    from .renderer import evaluation_path
+    if ds is not None:
+        camera = camera_path.dataset_camera(ds)
+    else:
+        fx = 0.5 * args.res / math.tan(0.5 * synthetic.CAMERA_ANGLE_X)
+        camera = dict(w=args.res, h=args.res, fx=fx, fy=fx, cx=args.res / 2, cy=args.res / 2, near_far=list(near_far))
+    if args.path in ("orbit", "spiral", "interp"):
+        if ds is not None:
+            c2ws = camera_path.from_dataset(ds, args.path, args.frames)
+        elif args.path == "orbit":
+            c2ws = camera_path.orbit(args.frames, (0.0, 0.0, 0.0), 4.0, 30.0)
+        else:
+            c2ws = camera_path.spiral(args.frames, (0.0, 0.0, 0.0), 4.0, (15.0, 45.0))
+    else:
+        c2ws, camera = camera_path.load_path(args.path, with_camera=True)
+        if "near_far" not in json.load(open(args.path)):
+            camera["near_far"] = list(near_far)
+    out = os.path.join(args.out, "path")
+    res = evaluation_path(None, nerf, c2ws, None, out, device=dev, noise=noise, panels=panels, animation=args.animation, fps=args.fps,
+                          camera=camera)
+    return dict(kind=args.path, dir=out, frames=res["frames"], panels=res["panels"], width=camera["w"], height=camera["h"],
+                seconds={k: round(v, 4) for k, v in res["seconds"].items()}, rays_per_s=round(res["rays_per_s"], 1))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", required=True)
@@ -124,7 +165,27 @@ def main(argv=None):
                     help="render view 0 N times under a yaw of 360 k / N of the lighting (light_000.png ... in --out)")
     ap.add_argument("--relight-eval", default=None, metavar="DIR",
                     help="with --datadir of an EXR test set: fit the brightness multiplier and write HDR frames, adjusted/ and stats.yaml")
+    ap.add_argument("--path", default=None, metavar="orbit|spiral|interp|FILE.json",
+                    help="render a camera path into --out/path/: a fly-around, a spiral, an interpolation through poses of the test "
+                         "set, or a transforms file written by an earlier run (transforms_path.json) or by hand")
+    ap.add_argument("--frames", type=int, default=120, help="frames of a generated --path")
+    ap.add_argument("--fps", type=float, default=30.0, help="frame rate of the path's animation")
+    ap.add_argument("--panels", default="rgb,depth", help="panels of a --path frame, from rgb,depth,normal,acc (rgb always)")
+    ap.add_argument("--animation", choices=("apng", "gif", "none"), default="apng",
+                    help="container of the path's video.png / depthvideo.png (an animated PNG), .gif, or none")
     args = ap.parse_args(argv)
+    if args.path:
+        if not args.out:
+            ap.error("--path needs --out (the frames go to OUT/path/)")
+        if args.frames < 1:
+            ap.error("--frames is at least 1")
+        path_panels = tuple(p for p in args.panels.split(",") if p)
+        if not path_panels or set(path_panels) - {"rgb", "depth", "normal", "acc"} or "rgb" not in path_panels:
+            ap.error("--panels is a comma-separated choice of rgb,depth,normal,acc that includes rgb")
+        if args.path == "interp" and not args.datadir:
+            ap.error("--path interp needs --datadir (it interpolates poses of the test set)")
+        if args.path not in ("orbit", "spiral", "interp") and not os.path.isfile(args.path):
+            ap.error(f"--path: '{args.path}' is neither orbit, spiral, interp nor a file")
     if args.light_turntable < 0:
         ap.error("--light-turntable takes a number of frames")
     if args.eval_dir and not args.datadir:
@@ -184,6 +245,8 @@ def main(argv=None):
         from .relight_eval import relight_evaluation
         res = relight_evaluation(nerf, ds, args.relight_eval, noise=noise, chunk=chunk)
         rec["relight"] = dict(psnr=round(res["psnr"], 3), ssim=round(res["ssim"], 5), multiplier=res["multiplier"], views=res["views"])
+    if args.path:
+        rec["path"] = render_path(nerf, args, ds if args.datadir else None, near_far, path_panels, noise, dev)
     print(json.dumps(rec), flush=True)
     return rec
 

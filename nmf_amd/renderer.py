@@ -1,6 +1,7 @@
 """Chunked rendering -- counterpart of the reference's renderer.py: `chunk_renderer` (:56-106, the callable train.py:541
 and BundleRender use), the evaluation PSNR (:399-401, :511-513) and the test-set evaluation `evaluation` / `evaluate`
-(:195-560: PSNR, SSIM and normal error per view, frames and mean.txt / stats.yaml)."""
+(:195-560: PSNR, SSIM and normal error per view, frames and mean.txt / stats.yaml), and the camera-path render `evaluation_path`
+(:564-582: views that are in no data set, rays and 8-bit frames made on the device, PNGs on a writer thread)."""
 import os
 import time
 from collections import defaultdict
@@ -250,3 +251,157 @@ def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=
     return evaluate(iterator, test_dataset, tensorf, renderer, savePath, prtx=prtx, N_samples=N_samples, white_bg=white_bg,
                     ndc_ray=ndc_ray, compute_extra_metrics=compute_extra_metrics, device=device, noise=noise,
                     material_maps=material_maps, **kw)
+
+
+PATH_PANELS = dict(rgb="rgb_map", depth="depth", normal="world_normal", acc="acc_map")       # panel -> key of render_images, in strip order
+PATH_DIRS = dict(depth="depth", normal="world_normal", acc="acc_map")                        # the folders of `evaluation`
+
+
+def _write_animation(path, frames, animation, fps):
+    """the reference's video.mp4 / depthvideo.mp4 (renderer.py:492-497, imageio) under their names as an animated PNG (or GIF)
+    written by Pillow: no video encoder is a dependency"""
+    from PIL import Image
+    ims = [Image.fromarray(a) for a in frames]
+    kw = dict(save_all=True, append_images=ims[1:], duration=1000.0 / fps, loop=0)
+    if animation == "apng":
+        ims[0].save(path + ".png", format="PNG", **kw)
+    else:
+        ims[0].save(path + ".gif", format="GIF", **kw)
+
+
+@torch.no_grad()
+def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="", device="cuda", noise=None, panels=("rgb", "depth"),
+                    animation="apng", fps=30, camera=None, writer_depth=2):
+    """renderer.py:564-582 (the call shape of train.py:884-901): renders the camera path c2ws [n, 4, 4] (camera-to-world, the loader's
+    convention; nmf_amd/camera_path.py) into savePath.  `renderer` is ignored, as in `evaluation`.  The camera is test_dataset's
+    (size, fx / fy, centred principal point, near_far) or camera = dict(w, h, fx, fy, cx, cy, near_far), with which test_dataset may
+    be None (a checkpoint rendered without a data set).
+
+    Per frame: the rays are made on the device from the pose (hip.camera_rays, one buffer for the whole path), rendered by
+    render_images with the keys the panels need, turned into ONE uint8 strip rgb | depth | normal | acc (hip.frame_finish: the 8-bit
+    conversions of `evaluation`; depth between near_far through hip.depth_colour_table) and copied into a pinned buffer without
+    blocking; a writer thread waits for the copy's event, slices the panels and encodes the PNGs while the next frame renders:
+    {prtx}{k:03d}.png (rgb, always a panel) and depth/, world_normal/, acc_map/ as in `evaluation`.  writer_depth bounds the frames
+    in flight (0: written on the calling thread); frames come out in order; an exception in the writer is raised here; the thread
+    is joined before the function returns.  At the end {prtx}video.png (and {prtx}depthvideo.png with a depth panel) hold the frames
+    as an animated PNG (animation="gif": .gif; "none": neither) and transforms_path.json the path (camera_path.save_path).
+    -> dict(frames, panels, seconds=dict(rays, render, finish: device time from events; write_wait: the calling thread blocked on
+    the writer; total: wall clock until the last frame is on disk; animation: the container), frame_ms=dict(rays, render, finish:
+    the device times per frame), rays_per_s)."""
+    import queue
+    import threading
+
+    from . import camera_path, hip
+    panels = tuple(p for p in PATH_PANELS if p in panels)
+    if "rgb" not in panels:
+        raise ValueError("evaluation_path: rgb is always a panel ({prtx}{k:03d}.png)")
+    if animation not in ("apng", "gif", "none"):
+        raise ValueError(f"evaluation_path: animation is apng, gif or none, got '{animation}'")
+    cam = dict(camera) if camera is not None else camera_path.dataset_camera(test_dataset)
+    W, H, near_far = int(cam["w"]), int(cam["h"]), cam["near_far"]
+    c2ws = np.asarray(c2ws.cpu() if isinstance(c2ws, torch.Tensor) else c2ws, dtype=np.float32)
+    n = c2ws.shape[0]
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    for sub in ("",) + tuple(PATH_DIRS[p] for p in panels if p in PATH_DIRS):
+        os.makedirs(os.path.join(savePath, sub), exist_ok=True)
+    keys = tuple(PATH_PANELS[p] for p in panels)
+    rays = torch.empty((H * W, 6), dtype=torch.float32, device=device)
+    strip = torch.empty((H, len(panels) * W, 3), dtype=torch.uint8, device=device)
+    pool = queue.Queue()
+    for _ in range(max(int(writer_depth), 0) + 1):
+        pool.put(torch.empty(strip.shape, dtype=torch.uint8).pin_memory())
+    kept = {p: [] for p in ("rgb", "depth") if p in panels and animation != "none"}
+    failure = []
+
+    def write(k, pin, done):
+        done.synchronize()
+        a = pin.numpy()
+        for j, p in enumerate(panels):
+            panel = a[:, j * W:(j + 1) * W]
+            _png(os.path.join(savePath, PATH_DIRS.get(p, ""), f"{prtx}{k:03d}.png"), panel)
+            if p in kept:
+                kept[p].append(panel.copy())
+
+    work = queue.Queue()
+
+    def writer():
+        while True:
+            item = work.get()
+            if item is None:
+                return
+            try:
+                if not failure:                       # (after a failure: only hand the buffers back, so that the caller never blocks)
+                    write(*item)
+            except BaseException as e:                # noqa: BLE001 -- raised again on the calling thread
+                failure.append(e)
+            finally:
+                pool.put(item[1])
+
+    thread = None
+    if writer_depth > 0:
+        thread = threading.Thread(target=writer, name="nmf-path-writer", daemon=True)
+        thread.start()
+    marks = []
+    t_wait = 0.0
+    was_training = tensorf.training
+    tensorf.eval()
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    try:
+        for k in range(n):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]      # rays 0-1, render 1-2, finish 3-4
+            ev[0].record()
+            hip.camera_rays(c2ws[k], cam["fx"], cam["fy"], cam["cx"], cam["cy"], H, W, out=rays)
+            ev[1].record()
+            ims = render_images(tensorf, rays, float(cam["fx"]), noise=noise, keys=keys)
+            ims = dict(rgb_map=ims) if keys == ("rgb_map",) else ims
+            ev[2].record()
+            tw = time.perf_counter()
+            pin = pool.get()                          # a free pinned buffer: blocks while writer_depth frames are in flight
+            t_wait += time.perf_counter() - tw
+            if failure:
+                pool.put(pin)
+                break
+            ev[3].record()
+            hip.frame_finish(H, W, **{p: ims[PATH_PANELS[p]] for p in panels}, near_far=near_far, out=strip)
+            ev[4].record()
+            pin.copy_(strip, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            marks.append(ev)
+            if thread is None:
+                tw = time.perf_counter()
+                try:
+                    write(k, pin, done)
+                finally:
+                    pool.put(pin)
+                t_wait += time.perf_counter() - tw
+            else:
+                work.put((k, pin, done))
+    finally:
+        if thread is not None:
+            tw = time.perf_counter()
+            work.put(None)
+            thread.join()
+            t_wait += time.perf_counter() - tw
+        tensorf.train(was_training)
+    if failure:
+        raise failure[0]
+    torch.cuda.synchronize(device)
+    total = time.perf_counter() - t0
+    frame_ms = {name: [e[i].elapsed_time(e[i + 1]) for e in marks] for name, i in (("rays", 0), ("render", 1), ("finish", 3))}
+    dev_s = [sum(frame_ms[name]) * 1e-3 for name in ("rays", "render", "finish")]
+    t1 = time.perf_counter()
+    if animation != "none" and n > 0:
+        _write_animation(os.path.join(savePath, f"{prtx}video"), kept["rgb"], animation, fps)
+        if "depth" in kept:
+            _write_animation(os.path.join(savePath, f"{prtx}depthvideo"), kept["depth"], animation, fps)
+    angle = 2.0 * float(np.arctan(0.5 * W / cam["fx"]))
+    camera_path.save_path(os.path.join(savePath, "transforms_path.json"), c2ws, angle, W, H, near_far,
+                          intrinsics=(cam["fx"], cam["fy"], cam["cx"], cam["cy"]))
+    return dict(frames=n, panels=list(panels),
+                seconds=dict(rays=dev_s[0], render=dev_s[1], finish=dev_s[2], write_wait=t_wait, total=total,
+                             animation=time.perf_counter() - t1),
+                frame_ms=frame_ms, rays_per_s=n * H * W / total if total > 0 else 0.0)

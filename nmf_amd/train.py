@@ -116,6 +116,9 @@ def main(argv=None):
     ap.add_argument("--material-maps", action="store_true",
                     help="with --render-test: also write the material maps of every test view (albedo/, roughness/, tint/, diffuse/, "
                          "spec/, rgbd/)")
+    ap.add_argument("--render-path", action="store_true",
+                    help="Blender scenes: render the test set's render_path (a 120-frame orbit) after training into "
+                         "<logfolder>/imgs_path_all/ (train.py:884-901); the override render_path=True does the same")
     ap.add_argument("--export-mesh", action="store_true",
                     help="after training: marching cubes of the alpha lattice into <logfolder>/<expname>.ply (nmf_amd.export_mesh)")
     ap.add_argument("-m", "--multirun", action="store_true",
@@ -149,6 +152,9 @@ def main(argv=None):
     ds = cfg["dataset"]
     if args.render_test and ds["dataset_name"] != "blender":
         ap.error(f"--render-test needs a Blender scene (--datadir or dataset=<scene>); dataset_name is {ds['dataset_name']}")
+    want_path = args.render_path or cfg.get("render_path") is True
+    if want_path and ds["dataset_name"] != "blender":
+        ap.error(f"--render-path / render_path=True needs a Blender scene (--datadir or dataset=<scene>); dataset_name is {ds['dataset_name']}")
     params = cfg["model"]["params"]
     n_iters = args.iters if args.iters is not None else (200 if shorthand else int(params["n_iters"]))
     eval_every = args.eval_every if args.eval_every is not None else (100 if shorthand else int(cfg["vis_every"]))
@@ -289,6 +295,12 @@ def main(argv=None):
         res = evaluation(te_all, nerf, None, None, os.path.join(logfolder, "imgs_test_all"), N_vis=-1, device=dev, noise=noise,
                          **(dict(material_maps=True) if args.material_maps else {}))
         print(json.dumps(dict(test_all=test_all_record(res))), flush=True)
+    if want_path and rank == 0:
+        from .renderer import evaluation_path
+        res = evaluation_path(te_set, nerf, te_set.render_path, None, os.path.join(logfolder, "imgs_path_all"), device=dev, noise=noise)
+        print(json.dumps(dict(path=dict(frames=res["frames"], panels=res["panels"],
+                                        seconds={k: round(v, 4) for k, v in res["seconds"].items()},
+                                        rays_per_s=round(res["rays_per_s"], 1)))), flush=True)
     if args.export_mesh and rank == 0:
         from .export_mesh import export
         os.makedirs(logfolder, exist_ok=True)
