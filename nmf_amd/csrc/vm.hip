@@ -1126,6 +1126,10 @@ struct FpRec {          // 4 x float4 per sample in LDS
 
 __device__ __forceinline__ void fp_prologue(const nmf_vm_params& p, const float4& x, bool valid, int i, int ox, int oy,
                                             int oz, float4& W, float4& Q, float4& L) {
+    // contract(off) as in make_tap2 / make_tap1: with `ix - floor(ix)` fused into fma(t, G - 1, -floor) the backward scattered with
+    // weights up to half an ulp of ix away from the forward's wherever G - 1 is not a power of two (percent-level for a tap with a small
+    // weight, a non-zero weight on the far tap of a sample that sits exactly on a texel: tests/test_hip_vm.py)
+#pragma clang fp contract(off)
     float xn[3];
     normalized(p, x, xn);
     const int G = p.grid;
