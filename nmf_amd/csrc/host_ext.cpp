@@ -884,7 +884,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> shade_mix_bwd_view(const Tens
 }
 
 Tensor ggx_rays_bwd_view(const Tensor& V, const Tensor& N, const Tensor& r, const Tensor& off, const Tensor& sobol,
-                         const Tensor& row_of_ray, const Tensor& j_of_ray, const Tensor& dL, const OT& d_rays,
+                         const Tensor& row_of_ray, const Tensor& j_of_ray, const OT& dL, const OT& d_rays,
                          int64_t stream) {
     TimedScope _ts(__func__, stream);
     const int64_t R = row_of_ray.size(0);
