@@ -38,7 +38,7 @@ extern "C" {
 
 /* Bumped with every incompatible change of a prototype or of a workspace size.  nmf_version() returns the value the LIBRARY
  * was built with; a separately built caller (nmf_amd/lib/_nmf_host.so) compares it with the value it was compiled against. */
-#define NMF_ABI_VERSION 124
+#define NMF_ABI_VERSION 125
 int nmf_version(void);
 const char* nmf_last_error_string(void);
 
@@ -655,6 +655,45 @@ int nmf_material_maps(const float* app, const float* normals, const float* weigh
                       float tint_bias, float f0_bias, float rough_bias, const float* conv, const int32_t* inv,
                       const int64_t* row_off, const int32_t* cnt, int64_t Mb, const float* incoming, const float* brdf_weight,
                       int64_t R, const float* acc, const float* bg, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Material edits: the heads' outputs changed at render time (evaluation only; nothing here has a backward).
+ * An edit list holds n_edits <= NMF_EDIT_MAX edits, applied in list order, each to the result of the one before.  An edit sees
+ * a sample's world position x (the frame of aabb and of the exported mesh) and its 11 head outputs v (nmf_heads_fwd).
+ *   target     albedo v[0:3] | f0 v[6:9] | roughness v[9] and v[10] (both alike).  The tint head v[3:6] is not editable.
+ *   region     all:        mask 1
+ *              box:        centre c, half extents h, d = max_i(|x_i - c_i| - h_i)
+ *              ellipsoid:  centre c, radii h, q_i = (x_i - c_i) / h_i, d = (sqrt((q0 q0 + q1 q1) + q2 q2) - 1) min(h)
+ *   mask       falloff == 0: m = d <= 0 ? 1 : 0;  falloff > 0: s = clamp(1 - d / falloff, 0, 1), m = (s s)(3 - 2 s);
+ *              invert: m = 1 - m
+ *   operator   colour targets: t_c = ((A_c0 v_0 + A_c1 v_1) + A_c2 v_2) + b_c, clamped to [0, 1]
+ *              roughness:      t_j = A_00 v_j + b_0, clamped to [0.01, 1] (the head's own clip)
+ *   blend      m == 0: the value keeps its bits;  m == 1: out = t;  otherwise out = v + m (t - v)
+ * fp32 with one rounding per operation in the order written, no fma: a float32 restatement that follows the same order gives the
+ * same bits (nmf_amd/edit.py apply_reference), and an identity edit (A = I, b = 0) returns its input bits.
+ *
+ * The table `edits` is HOST memory, [n_edits][NMF_EDIT_ROW] fp32; it is checked and then travels in the kernel arguments:
+ *   0 kind (0 all, 1 box, 2 ellipsoid) | 1 target (0 albedo, 1 f0, 2 roughness) | 2 invert (0 / 1) | 3 falloff | 4-6 c | 7-9 h |
+ *   10-18 A row-major | 19-21 b | 22-31 zero
+ * Checked before anything is launched: n_edits > NMF_EDIT_MAX, an entry that is not finite, a kind / target / invert outside the
+ * values above, falloff < 0, h <= 0 for a box or an ellipsoid: NMF_ERANGE.  Null pointers, negative sizes, xyz_stride other than
+ * 3 or 4: NMF_EINVAL.
+ *
+ * nmf_heads_edit: heads [n][11] (device) edited in place; xyz [n][xyz_stride] (device; 4: the xyzt rows the passes carry, the
+ * fourth column is not read).  n == 0 or n_edits == 0: nothing is launched.  One launch: a lane per row, a workgroup's 256 rows
+ * moved through LDS with coalesced dword accesses.
+ * nmf_material_maps_edit: nmf_material_maps with the edits applied to every sample's head outputs right after they are evaluated
+ * (xyz [M][xyz_stride]: the samples' positions).  n_edits == 0: the launch and the bits of nmf_material_maps (xyz may be NULL).
+ * ---------------------------------------------------------------------------------------- */
+#define NMF_EDIT_ROW 32
+#define NMF_EDIT_MAX 16
+int nmf_heads_edit(float* heads, const float* xyz, int32_t xyz_stride, int64_t n, const float* edits, int32_t n_edits, void* stream);
+int nmf_material_maps_edit(const float* app, const float* normals, const float* weight, const int64_t* offsets, int64_t B, int64_t M,
+                           const float* rays, const float* head_W, const float* head_b, float diffuse_mul, float diffuse_bias,
+                           float tint_bias, float f0_bias, float rough_bias, const float* conv, const int32_t* inv,
+                           const int64_t* row_off, const int32_t* cnt, int64_t Mb, const float* incoming, const float* brdf_weight,
+                           int64_t R, const float* acc, const float* bg, float* out, const float* xyz, int32_t xyz_stride,
+                           const float* edits, int32_t n_edits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mesh export: indexed marching cubes over a dense volume (the reference's scripts/export_mesh.py runs

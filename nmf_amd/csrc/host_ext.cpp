@@ -340,18 +340,59 @@ Tensor brdf_mlp_pack(const std::vector<Tensor>& w, const OT& into, int64_t strea
     return img;
 }
 
+// ---- material edits (nmf_heads_edit, nmf_material_maps_edit): the table is read on the HOST by the C ABI ------------------------
+// -> a contiguous host fp32 copy of `edits` [K,32] (a device table is copied back: callers on a hot path keep a host table)
+static Tensor edit_table(const OT& edits, int64_t& K) {
+    K = 0;
+    if (!edits.has_value() || !edits->defined() || edits->numel() == 0) return Tensor();
+    if (edits->dim() != 2 || edits->size(1) != NMF_EDIT_ROW || edits->scalar_type() != at::kFloat) fail("material edits: the table is fp32 [K,32]");
+    K = edits->size(0);
+    return edits->to(at::kCPU).contiguous();
+}
+
+// heads [n,11] edited in place at the positions xyz [n,3] / [n,4]
+void heads_edit(const Tensor& heads, const Tensor& xyz, const OT& edits, int64_t stream) {
+    TimedScope _ts(__func__, stream);
+    int64_t K = 0;
+    Tensor tab = edit_table(edits, K);
+    if (heads.dim() != 2 || heads.size(1) != 11) fail("heads_edit: heads is [n,11]");
+    const int64_t n = heads.size(0);
+    if (xyz.dim() != 2 || xyz.size(0) != n || (xyz.size(1) != 3 && xyz.size(1) != 4)) fail("heads_edit: xyz is [n,3] or [n,4]");
+    check(nmf_heads_edit(ptr<float>(heads, at::kFloat), f32(xyz), (int32_t)xyz.size(1), n, K ? static_cast<const float*>(tab.data_ptr()) : nullptr, (int32_t)K,
+                         st(stream)),
+          "nmf_heads_edit");
+}
+
 // ---- material maps of the evaluation pass (nmf_material_maps) -----------------------------------------------------------
 // -> [B,15]: albedo | roughness | diffuse | tint | spec, 3 columns each
 Tensor material_maps(const Tensor& app, const Tensor& normals, const Tensor& w, const Tensor& offsets, const Tensor& rays,
                      const Tensor& W, const Tensor& b, const std::vector<double>& hp, const Tensor& conv, const OT& inv,
                      const OT& row_off, const OT& cnt, const OT& incoming, const OT& brdf_weight, const Tensor& acc,
-                     const Tensor& bg, int64_t stream) {
+                     const Tensor& bg, int64_t stream, const OT& xyz = OT(), const OT& edits = OT()) {
     // inv / row_off / cnt / incoming / brdf_weight all absent: no bounce row (Mb = R = 0), tint and spec are 0
+    // edits (host fp32 [K,32], nmf_hip.h "Material edits") with xyz ([M,3] or [M,4], the samples' positions): nmf_material_maps_edit
     TimedScope _ts(__func__, stream);
     if (hp.size() != 5) fail("material_maps: hp = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)");
     const int64_t B = offsets.size(0) - 1, M = app.size(0);
     const int64_t Mb = row_off.has_value() ? row_off->size(0) - 1 : 0, R = incoming.has_value() ? incoming->size(0) : 0;
     Tensor o = fe(app, {B, 15});
+    if (edits.has_value() || xyz.has_value()) {
+        int64_t K = 0, stride = 3;
+        Tensor tab = edit_table(edits, K);
+        if (xyz.has_value()) {
+            if (xyz->dim() != 2 || xyz->size(0) != M || (xyz->size(1) != 3 && xyz->size(1) != 4)) fail("material_maps: xyz is [M,3] or [M,4]");
+            stride = xyz->size(1);
+        } else if (K > 0) {
+            fail("material_maps: edits need the samples' positions xyz");
+        }
+        check(nmf_material_maps_edit(f32(app), f32(normals), f32(w), i64(offsets), B, M, f32(rays), f32(W), f32(b), (float)hp[0],
+                                     (float)hp[1], (float)hp[2], (float)hp[3], (float)hp[4], f32(conv), optr<const int32_t>(inv, at::kInt),
+                                     optr<const int64_t>(row_off, at::kLong), optr<const int32_t>(cnt, at::kInt), Mb, of32(incoming),
+                                     of32(brdf_weight), R, f32(acc), f32(bg), out(o), of32(xyz), (int32_t)stride,
+                                     K ? static_cast<const float*>(tab.data_ptr()) : nullptr, (int32_t)K, st(stream)),
+              "nmf_material_maps_edit");
+        return o;
+    }
     check(nmf_material_maps(f32(app), f32(normals), f32(w), i64(offsets), B, M, f32(rays), f32(W), f32(b), (float)hp[0], (float)hp[1],
                             (float)hp[2], (float)hp[3], (float)hp[4], f32(conv), optr<const int32_t>(inv, at::kInt),
                             optr<const int64_t>(row_off, at::kLong), optr<const int32_t>(cnt, at::kInt), Mb, of32(incoming),
@@ -1180,7 +1221,10 @@ PYBIND11_MODULE(_nmf_host, m) {
     m.def("brdf_mlp_bwd_sets", &brdf_mlp_bwd_sets, py::arg("w"), py::arg("sets"), py::arg("grads"), py::arg("max_workgroups"), py::arg("stream"),
           py::arg("image") = py::none());
     m.def("heads_fwd", &heads_fwd);
-    m.def("material_maps", &material_maps);
+    m.def("material_maps", &material_maps, py::arg("app"), py::arg("normals"), py::arg("w"), py::arg("offsets"), py::arg("rays"), py::arg("W"),
+          py::arg("b"), py::arg("hp"), py::arg("conv"), py::arg("inv"), py::arg("row_off"), py::arg("cnt"), py::arg("incoming"),
+          py::arg("brdf_weight"), py::arg("acc"), py::arg("bg"), py::arg("stream"), py::arg("xyz") = py::none(), py::arg("edits") = py::none());
+    m.def("heads_edit", &heads_edit);
     m.def("ggx_rays_fwd", &ggx_rays_fwd);
     m.def("shade_mix_fwd", &shade_mix_fwd);
     m.def("bounce_index", &bounce_index, py::arg("counts"), py::arg("xyzt"), py::arg("stream"), py::arg("pub") = 0, py::arg("pub_seq") = 0,
@@ -1232,6 +1276,8 @@ PYBIND11_MODULE(_nmf_host, m) {
         .def("has_pending", &StepCore::has_pending)
         .def("render", &StepCore::render, py::arg("rays"), py::arg("focal"), py::arg("noise"), py::arg("want_maps"),
              py::arg("want_materials") = false, py::arg("want_linear") = false)
+        .def("set_material_edits", &StepCore::set_material_edits)
+        .def("n_material_edits", &StepCore::n_material_edits)
         .def("begin_step", &StepCore::begin_step)
         .def("join_env_table_backward", &StepCore::join_env_table_backward)
         .def("env_was_used", &StepCore::env_was_used)

@@ -10,6 +10,9 @@
 // evaluates the heads, the irradiance, the Fresnel term and its row's means in registers; the group sums with a fixed shuffle tree.
 // The only global writes are the 15 floats of the ray.  W and b of the heads and the 27 SH coefficients sit in LDS (heads.hip:59-62:
 // as uniform global addresses they become more scalar loads than the scalar registers hold).
+#include <type_traits>
+
+#include "edit_eval.hpp"
 #include "heads_eval.hpp"
 #include "rows_bwd.hpp"
 
@@ -36,10 +39,22 @@ struct MapsIn {
     const float* bg;            // [3]
 };
 
-template <int W>
+// the material edits of nmf_material_maps_edit: the samples' positions and the table (by value, edit_eval.hpp); NoEdit is what the
+// kernel of nmf_material_maps takes in its place (the EDIT = false instantiation has the code it had before edits existed)
+struct EditIn {
+    const float* xyz;           // [M][xyz_stride]
+    int32_t xyz_stride;
+    nmf_edit::Table tab;
+};
+struct NoEdit {
+    int32_t unused;
+};
+
+template <int W, bool EDIT>
 __global__ void __launch_bounds__(256) k_material_maps(MapsIn in, int64_t B, const float* __restrict__ head_W,
                                                        const float* __restrict__ head_b, HeadP hp, const float* __restrict__ conv,
-                                                       float* __restrict__ out) {
+                                                       float* __restrict__ out,
+                                                       typename std::conditional<EDIT, EditIn, NoEdit>::type ed) {
 #pragma clang fp contract(off)
     __shared__ float s_W[O * F];
     __shared__ float s_b[O];
@@ -73,6 +88,10 @@ __global__ void __launch_bounds__(256) k_material_maps(MapsIn in, int64_t B, con
         int z = 0;
         asm volatile("" : "+v"(z));
         nmf_heads::heads_eval(f, s_W + z, s_b + z, hp, h);
+        if constexpr (EDIT) {
+            const float* __restrict__ p = ed.xyz + k * (int64_t)ed.xyz_stride;
+            nmf_edit::edit_apply(h, p[0], p[1], p[2], ed.tab);
+        }
         const float nx = in.normals[k * 3], ny = in.normals[k * 3 + 1], nz = in.normals[k * 3 + 2];
         float Y[9];
         nmf_rows::sh9(nx, ny, nz, Y);
@@ -123,6 +142,28 @@ __global__ void __launch_bounds__(256) k_material_maps(MapsIn in, int64_t B, con
     }
 }
 
+template <bool EDIT>
+int launch_maps(const char* who, const float* app, const float* normals, const float* weight, const int64_t* offsets, int64_t B, int64_t M,
+                const float* rays, const float* head_W, const float* head_b, const HeadP& hp, const float* conv, const int32_t* inv,
+                const int64_t* row_off, const int32_t* cnt, int64_t Mb, const float* incoming, const float* brdf, const float* acc,
+                const float* bg, float* out, void* stream, const typename std::conditional<EDIT, EditIn, NoEdit>::type& ed) {
+    const MapsIn in{app, normals, weight, offsets, rays, Mb > 0 ? inv : nullptr, row_off, cnt, incoming, brdf, acc, bg};
+    // lanes per ray from the mean samples per ray: about two samples per lane, whole waves of 64 at most
+    const int64_t avg = B > 0 ? M / B : 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (avg >= 64)
+        NMF_LAUNCH_NAMED(EDIT ? "k_material_maps_edit<64>" : "k_material_maps<64>", (k_material_maps<64, EDIT>), dim3((unsigned)cdiv(B, 4)),
+                         dim3(256), 0, st, in, B, head_W, head_b, hp, conv, out, ed);
+    else if (avg >= 16)
+        NMF_LAUNCH_NAMED(EDIT ? "k_material_maps_edit<16>" : "k_material_maps<16>", (k_material_maps<16, EDIT>), dim3((unsigned)cdiv(B, 16)),
+                         dim3(256), 0, st, in, B, head_W, head_b, hp, conv, out, ed);
+    else
+        NMF_LAUNCH_NAMED(EDIT ? "k_material_maps_edit<8>" : "k_material_maps<8>", (k_material_maps<8, EDIT>), dim3((unsigned)cdiv(B, 32)),
+                         dim3(256), 0, st, in, B, head_W, head_b, hp, conv, out, ed);
+    NMF_CHECK_LAUNCH(who);
+    return NMF_OK;
+}
+
 }  // namespace
 
 extern "C" int nmf_material_maps(const float* app, const float* normals, const float* weight, const int64_t* offsets, int64_t B,
@@ -136,17 +177,34 @@ extern "C" int nmf_material_maps(const float* app, const float* normals, const f
     NMF_REQUIRE(offsets && rays && head_W && head_b && conv && acc && bg && out, NMF_EINVAL, "nmf_material_maps: null");
     NMF_REQUIRE(M == 0 || (app && normals && weight), NMF_EINVAL, "nmf_material_maps: null sample input");
     NMF_REQUIRE(Mb == 0 || (inv && row_off && cnt && incoming && brdf_weight), NMF_EINVAL, "nmf_material_maps: null row input");
-    const MapsIn in{app, normals, weight, offsets, rays, Mb > 0 ? inv : nullptr, row_off, cnt, incoming, brdf_weight, acc, bg};
     const HeadP hp{diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias};
-    // lanes per ray from the mean samples per ray: about two samples per lane, whole waves of 64 at most
-    const int64_t avg = B > 0 ? M / B : 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (avg >= 64)
-        NMF_LAUNCH(k_material_maps<64>, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, in, B, head_W, head_b, hp, conv, out);
-    else if (avg >= 16)
-        NMF_LAUNCH(k_material_maps<16>, dim3((unsigned)cdiv(B, 16)), dim3(256), 0, st, in, B, head_W, head_b, hp, conv, out);
-    else
-        NMF_LAUNCH(k_material_maps<8>, dim3((unsigned)cdiv(B, 32)), dim3(256), 0, st, in, B, head_W, head_b, hp, conv, out);
-    NMF_CHECK_LAUNCH("nmf_material_maps");
-    return NMF_OK;
+    return launch_maps<false>("nmf_material_maps", app, normals, weight, offsets, B, M, rays, head_W, head_b, hp, conv, inv, row_off, cnt, Mb,
+                              incoming, brdf_weight, acc, bg, out, stream, NoEdit{0});
+}
+
+extern "C" int nmf_material_maps_edit(const float* app, const float* normals, const float* weight, const int64_t* offsets, int64_t B,
+                                      int64_t M, const float* rays, const float* head_W, const float* head_b, float diffuse_mul,
+                                      float diffuse_bias, float tint_bias, float f0_bias, float rough_bias, const float* conv,
+                                      const int32_t* inv, const int64_t* row_off, const int32_t* cnt, int64_t Mb, const float* incoming,
+                                      const float* brdf_weight, int64_t R, const float* acc, const float* bg, float* out,
+                                      const float* xyz, int32_t xyz_stride, const float* edits, int32_t n_edits, void* stream) {
+    NMF_REQUIRE(B >= 0 && M >= 0 && Mb >= 0 && R >= 0, NMF_EINVAL, "nmf_material_maps_edit: negative size");
+    NMF_REQUIRE(Mb <= M && Mb <= R && (Mb > 0 || R == 0), NMF_EINVAL, "nmf_material_maps_edit: need Mb <= M, Mb <= R, R == 0 without rows");
+    NMF_REQUIRE(xyz_stride == 3 || xyz_stride == 4, NMF_EINVAL, "nmf_material_maps_edit: xyz_stride must be 3 or 4");
+    EditIn ed;
+    const int rc = nmf_edit::load_table(edits, n_edits, ed.tab, "nmf_material_maps_edit");
+    if (rc != NMF_OK) return rc;
+    if (B == 0) return NMF_OK;
+    NMF_REQUIRE(offsets && rays && head_W && head_b && conv && acc && bg && out, NMF_EINVAL, "nmf_material_maps_edit: null");
+    NMF_REQUIRE(M == 0 || (app && normals && weight), NMF_EINVAL, "nmf_material_maps_edit: null sample input");
+    NMF_REQUIRE(Mb == 0 || (inv && row_off && cnt && incoming && brdf_weight), NMF_EINVAL, "nmf_material_maps_edit: null row input");
+    NMF_REQUIRE(n_edits == 0 || M == 0 || xyz, NMF_EINVAL, "nmf_material_maps_edit: null positions");
+    const HeadP hp{diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias};
+    if (n_edits == 0)          // the launch of nmf_material_maps itself
+        return launch_maps<false>("nmf_material_maps_edit", app, normals, weight, offsets, B, M, rays, head_W, head_b, hp, conv, inv, row_off,
+                                  cnt, Mb, incoming, brdf_weight, acc, bg, out, stream, NoEdit{0});
+    ed.xyz = xyz;
+    ed.xyz_stride = xyz_stride;
+    return launch_maps<true>("nmf_material_maps_edit", app, normals, weight, offsets, B, M, rays, head_W, head_b, hp, conv, inv, row_off, cnt,
+                             Mb, incoming, brdf_weight, acc, bg, out, stream, ed);
 }

@@ -147,6 +147,8 @@ class StepCore {
     // train.py:509-747, calls forward, forms its loss with torch and calls backward()).
     // -> dict(kept, n_samples, [rgb_map, acc, ori, whole_valid, n_rays, n_rows]); n_samples == [0]: nothing to back-propagate
     py::dict train_forward(const Tensor& rays, double focal, py::object noise) {
+        if (n_edits_ > 0) throw py::value_error("material edits are set: they are an evaluation feature and never enter a gradient "
+                                                "(set_material_edits(None) before training)");
         pending_.reset();
         begin(noise);
         auto t = fwd(0, rays, focal, OT(), noise, true);
@@ -275,7 +277,28 @@ class StepCore {
         return out;
     }
 
+    // ---- material edits of the evaluation pass (nmf_heads_edit / nmf_material_maps_edit) ---------------------------------------
+    // table: fp32 [K,32] (any device; a host copy is kept and checked by the C ABI at each use), or None / K = 0 for no edits.
+    // Read only when !is_train: with edits every recursion level evaluates its heads in a launch of their own, edits them in place
+    // and prepares the bounce rows from them (the unfused pair nmf_hip.h documents as bit-equal to nmf_bounce_prep_fwd_heads),
+    // and the material maps take the _edit entry.  Without edits nothing changes: the same launches, the same bits.
+    void set_material_edits(const OT& table) {
+        if (!table.has_value() || !table->defined() || table->numel() == 0) {
+            edits_ = Tensor();
+            n_edits_ = 0;
+            return;
+        }
+        if (table->dim() != 2 || table->size(1) != NMF_EDIT_ROW || table->scalar_type() != at::kFloat)
+            throw py::value_error("set_material_edits: the table is fp32 [K,32]");
+        if (table->size(0) > NMF_EDIT_MAX) throw py::value_error("set_material_edits: at most 16 edits");
+        edits_ = table->detach().to(at::kCPU).contiguous().clone();
+        n_edits_ = edits_.size(0);
+    }
+    int64_t n_material_edits() const { return n_edits_; }
+
   private:
+    Tensor edits_;                 // host fp32 [K,32]
+    int64_t n_edits_ = 0;
     // the material maps of level 0: appearance features of every kept sample (the forward query with appearance only), then
     // nmf_material_maps over the samples, their dense normals and the level's bounce rows
     Tensor material_maps_(CoreLevel& t) {
@@ -291,11 +314,13 @@ class StepCore {
         Tensor nr = t.nr->contiguous(), w = t.w.contiguous(), inv = t.inv.narrow(0, 0, M).contiguous();
         Tensor incoming = t.incoming.contiguous(), brdf = t.brdf->contiguous(), conv = t.conv.contiguous();
         Tensor maps = material_maps(app, nr, w, t.offsets.contiguous(), rays, head_W, head_b, head_p, conv, inv, t.row_off.contiguous(),
-                                    t.cnt32.contiguous(), incoming, brdf, t.acc.contiguous(), t.bg.contiguous(), main_stream);
+                                    t.cnt32.contiguous(), incoming, brdf, t.acc.contiguous(), t.bg.contiguous(), main_stream, OT(xyzt),
+                                    n_edits_ > 0 ? OT(edits_) : OT());
         if (!trace_.is_none()) {       // tests: the inputs of the maps, for a restatement in float64
             trace_put("mm_app0", app); trace_put("mm_normals0", nr); trace_put("mm_w0", w); trace_put("mm_offsets0", t.offsets);
             trace_put("mm_rays0", rays); trace_put("mm_inv0", inv); trace_put("mm_row_off0", t.row_off); trace_put("mm_cnt0", t.cnt32);
             trace_put("mm_incoming0", incoming); trace_put("mm_brdf0", brdf); trace_put("mm_conv0", conv); trace_put("mm_acc0", t.acc);
+            trace_put("mm_xyzt0", xyzt);
         }
         return maps;
     }
@@ -653,9 +678,17 @@ class StepCore {
                                            false, true, false, main_stream));
         Tensor xyz;
         env_ready();                 // the material heads are evaluated inside the row preparation (one launch per level)
-        std::tie(t->heads, t->V, t->N, t->r1, t->f0, t->diff, t->feat, xyz) =
-            bounce_prep_fwd_heads(t->bidx, *t->nr, t->app, head_W, head_b, head_p, S.xyzt, S.ray_id, S.rays, t->conv, feat_noise, anoise,
-                                  is_train ? min_rough : -1e30, sparse_n ? 2 : 1, main_stream);
+        if (!is_train && n_edits_ > 0) {   // material edits: heads, edit in place, row preparation from the edited heads
+            t->heads = heads_fwd(t->app, head_W, head_b, head_p, main_stream);
+            heads_edit(t->heads, t->xyz_rows, edits_, main_stream);
+            std::tie(t->V, t->N, t->r1, t->f0, t->diff, t->feat, xyz) =
+                bounce_prep_fwd(t->bidx, *t->nr, t->app, t->heads, S.xyzt, S.ray_id, S.rays, t->conv, feat_noise, anoise, -1e30,
+                                sparse_n ? 2 : 1, main_stream);
+        } else {
+            std::tie(t->heads, t->V, t->N, t->r1, t->f0, t->diff, t->feat, xyz) =
+                bounce_prep_fwd_heads(t->bidx, *t->nr, t->app, head_W, head_b, head_p, S.xyzt, S.ray_id, S.rays, t->conv, feat_noise,
+                                      anoise, is_train ? min_rough : -1e30, sparse_n ? 2 : 1, main_stream);
+        }
         std::tie(t->L, t->hl, t->dl, t->lpdf, t->mip, t->brays) =
             ggx_rays_fwd(t->V, t->N, t->r1, xyz, t->off, t->cnt32, sobol, t->row_of_ray, t->j_of_ray, main_stream);
         const bool has_retrace = lvl < (int)max_retrace_rays.size();

@@ -41,14 +41,21 @@ def main(argv=None):
     ap.add_argument("--reference-spacing", action="store_true",
                     help="place the vertices as the reference does: aabb[0] + idx * size / G instead of size / (G - 1)")
     ap.add_argument("--output", default=None, help="default: the checkpoint path with .th replaced by .ply")
+    from . import edit
+    edit.add_arguments(ap)
     args = ap.parse_args(argv)
     if args.resolution is not None and len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one value or three")
+    try:
+        material_edits = edit.from_args(args)
+    except (edit.EditError, OSError) as e:
+        ap.error(str(e))
     from .modules.tensor_nerf import TensorNeRF
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
     nerf = TensorNeRF.load(args.ckpt, device=dev)
     nerf.eval()
+    nerf.set_material_edits(material_edits)          # the vertex attributes carry the edited materials
     res = None if args.resolution is None else (args.resolution[0] if len(args.resolution) == 1 else args.resolution)
     rec = export(nerf, args.output or default_output(args.ckpt), res, args.level, not args.no_attributes, args.reference_spacing)
     print(json.dumps(rec), flush=True)

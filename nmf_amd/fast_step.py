@@ -184,7 +184,7 @@ class TrainPass:
                 if main is None:
                     main = self._side[("ctx", k, "main")] = torch.cuda.Stream()
             self._ctxs.append(_ns(index=k, core=hip.HOST_EXT.StepCore(), main=main, key=None, keep=None, static=None, march_blocks=None,
-                                  retrace=None, acc=None, bound=-1))
+                                  retrace=None, acc=None, bound=-1, edits=None))
             for name, v in self._switches.items():
                 setattr(self._ctxs[-1].core, name, v)
         return self._ctxs[i]
@@ -360,6 +360,10 @@ class TrainPass:
             c.march_p0, c.march_p1 = ctypes.addressof(blk0[1]), ctypes.addressof(blk1[1])
             c.alpha_bits, c.alpha_coarse = (packed[1], packed[2]) if packed is not None else (None, None)
         c.min_rough, c.detach_n = float(model.min_rough), bool(model.detach_N)
+        edits = getattr(n, "_material_edit_table", None)          # TensorNeRF.set_material_edits (evaluation only: a training call
+        if edits is not cx.edits:                                 # with edits raises inside the core)
+            cx.edits = edits
+            c.set_material_edits(edits)
         mr = [int(v) for v in model.max_retrace_rays]
         if mr != cx.retrace:
             cx.retrace = mr

@@ -94,7 +94,7 @@ EXPORTS = [
     "nmf_loss_mix_fwd", "nmf_loss_mix_bwd", "nmf_loss_head", "nmf_loss_head_workspace_bytes", "nmf_bg_adjoint", "nmf_vm_query_bwd_segments", "nmf_vm_bwd_clean_bytes", "nmf_sh_project",
     "nmf_retrace_scores", "nmf_argsort_f32", "nmf_argsort_workspace_bytes", "nmf_topk_select", "nmf_topk_select_workspace_bytes", "nmf_alpha_coarse", "nmf_alpha_coarse_words", "nmf_bounce_index_select", "nmf_bounce_prep_fwd_heads", "nmf_bounce_prep_heads_bwd", "nmf_multi_copy",
     "nmf_ssim", "nmf_ssim_workspace_bytes", "nmf_normal_err", "nmf_normal_err_workspace_bytes",
-    "nmf_material_maps",
+    "nmf_material_maps", "nmf_material_maps_edit", "nmf_heads_edit",
     "nmf_mc_count", "nmf_mc_emit", "nmf_mc_workspace_bytes", "nmf_mc_case_triangles",
     "nmf_tv_fwd_bwd", "nmf_tv_workspace_bytes",
     "nmf_env_resample",
@@ -998,17 +998,29 @@ def relight_adjust(pred, gt, multi):
 MATERIAL_MAPS = ("albedo", "roughness", "diffuse", "tint", "spec")          # the [B,15] block of nmf_material_maps, 3 columns each
 
 
+def heads_edit(heads, xyz, edits):
+    """nmf_heads_edit: the material edits `edits` (fp32 [K,32], nmf_amd.edit.pack; read on the host, so a host table costs no
+    copy) applied IN PLACE to the head rows `heads` [n,11] of the samples at the world positions xyz [n,3] or [n,4] (xyzt rows; the
+    fourth column is not read).  None or K = 0: nothing is launched.  -> heads"""
+    _p(heads, torch.float32)        # refuses host tensors before the stream is asked for (there is none without a GPU)
+    _p(xyz, torch.float32)
+    HOST_EXT.heads_edit(heads, xyz, edits, _stream())
+    return heads
+
+
 def material_maps(app, normals, weight, offsets, rays, head_W, head_b, head_p, conv, acc, bg, inv=None, row_off=None, cnt=None,
-                  incoming=None, brdf_weight=None):
+                  incoming=None, brdf_weight=None, xyz=None, edits=None):
     """nmf_material_maps: the level-0 material maps of B rays from their M kept samples -> fp32 [B,15] (albedo | roughness |
     diffuse | tint | spec, 3 columns each).  app [M,24], normals [M,3], weight [M], offsets int64 [B+1], rays [B,6], head_W [11,24],
     head_b [11], head_p = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias), conv [9,3], acc [B], bg [3]; the bounce rows
-    inv int32 [M], row_off int64 [Mb+1], cnt int32 [Mb], incoming / brdf_weight [R,3] (all None: no row, spec and tint are 0)."""
+    inv int32 [M], row_off int64 [Mb+1], cnt int32 [Mb], incoming / brdf_weight [R,3] (all None: no row, spec and tint are 0).
+    edits (fp32 [K,32], nmf_amd.edit.pack) with xyz [M,3] or [M,4], the samples' positions: nmf_material_maps_edit, the edits applied
+    to each sample's head outputs (K = 0: the bits of the call without them)."""
     _p(app, torch.float32)          # refuses host tensors before the stream is asked for (there is none without a GPU)
     if len(head_p) != 5:
         raise NmfHipError("material_maps: head_p = (diffuse_mul, diffuse_bias, tint_bias, f0_bias, rough_bias)")
     return HOST_EXT.material_maps(app, normals, weight, offsets, rays, head_W, head_b, [float(v) for v in head_p], conv, inv, row_off, cnt,
-                                  incoming, brdf_weight, acc, bg, _stream())
+                                  incoming, brdf_weight, acc, bg, _stream(), xyz, edits)
 
 
 # ---- mesh export: marching cubes over a dense volume (csrc/mesh.hip) ------------------------------------------------------

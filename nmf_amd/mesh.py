@@ -63,6 +63,9 @@ def vertex_attributes(nerf, xyz):
     for s in range(0, xyz.shape[0], ATTRIBUTE_CHUNK):
         p = xyz[s:s + ATTRIBUTE_CHUNK].contiguous()
         heads = nerf.model.diffuse_module.heads(nerf.rf.compute_appfeature(p))
+        table = getattr(nerf, "_material_edit_table", None)
+        if table is not None:                  # nerf.set_material_edits: the attributes of the edited materials
+            heads = hip.heads_edit(heads.detach().contiguous(), p, table)
         for o, v in zip(outs, (nerf.rf.compute_normals(p), heads[:, 0:3], heads[:, 6:9], heads[:, 9])):
             o.append(v.detach())
     if not outs[0]:

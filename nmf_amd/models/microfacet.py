@@ -144,8 +144,11 @@ class Microfacet(FastPrivateAttrs, torch.nn.Module):
             deferred = noise.normal_deferred((M, 24))                                               # :297, rows drawn later
         noise.skip("randn", (M, 3))
         noise.skip("randn", (M, 2))
+        edits = None if is_train else getattr(self, "_material_edit_table", None)      # TensorNeRF.set_material_edits
         if not sparse:
             heads = self.diffuse_module.heads(app_features)                                          # :299
+            if edits is not None:
+                heads = hip.heads_edit(heads.detach().contiguous(), samples.xyzt, edits)
         noise.skip("rand", (5000,))                                                                 # :304-315
         noise.skip("rand", (5000,))
         _, conv = bg_module.get_spherical_harmonics(100)
@@ -175,6 +178,7 @@ class Microfacet(FastPrivateAttrs, torch.nn.Module):
         bidx, row_off, cnt32, inv, tot = hip.bounce_index(counts)                                    # :333-350
         R, Mb = (int(v) for v in tot.cpu())
         out = Shaded(self, samples, heads, normals, conv, w_det, inv, M, app_fn)
+        out.edits = edits
         if R == 0:
             return out
         bidx, row_off, cnt32 = bidx[:Mb], row_off[:Mb + 1], cnt32[:Mb]
@@ -265,6 +269,7 @@ class Shaded:
         self.mix_args = None          # inputs of the Fresnel mix when the row radiance has not been formed yet
         self.rows = None
         self._debug = None
+        self.edits = None             # material edits of an evaluation pass (applied to heads evaluated here on demand)
 
     @property
     def refl_rows(self):
@@ -286,6 +291,8 @@ class Shaded:
         if self._debug is None:
             if self.heads is None:          # sparse evaluation: the per-sample material maps were not needed so far
                 self.heads = self.model.diffuse_module.heads(self.app_fn(self.samples.xyzt))
+                if self.edits is not None:
+                    self.heads = hip.heads_edit(self.heads.detach().contiguous(), self.samples.xyzt, self.edits)
             S, h, n = self.samples, self.heads, self.normals
             albedo, f0, r1 = h[:, 0:3], h[:, 6:9], h[:, 9:10]
             viewdirs = torch.index_select(S.rays[:, 3:6], 0, S.ray_id.long())

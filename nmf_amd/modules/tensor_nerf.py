@@ -50,6 +50,20 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
         self._fused_pass = None
         self.operator_graph_forwards = 0        # training forwards (recur 0, CUDA, grad mode) that built the operator graph
         self.regulariser_weights = None         # optional {stat name: weight} of the caller's loss: a fused forward refuses a non-zero one
+        # render-time material edits (nmf_amd/edit.py): plain attributes, never in the state_dict or a checkpoint
+        self.material_edits = []
+        self._material_edit_table = None        # host fp32 [K,32] (edit.pack), None without edits: what every consumer reads
+
+    def set_material_edits(self, edits):
+        """edits: a list of nmf_amd.edit.MaterialEdit (at most 16, applied in order), or None / [] for none.  Evaluation renders
+        (module path and fused pass, every recursion level), the material maps and mesh.vertex_attributes then see the edited albedo,
+        f0 and roughness; a training call raises ValueError while edits are set."""
+        from .. import edit
+        edits = list(edits or ())
+        table = edit.pack(edits, "cpu") if edits else None          # (validates the list)
+        self.material_edits = edits
+        self._material_edit_table = table
+        self.model._material_edit_table = table                      # Microfacet.shade_compact reads it for evaluation passes
 
     def get_device(self):
         return self.rf.units.device
@@ -125,6 +139,9 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
                 override_near=None, output_alpha=None, dynamic_batch_size=True, gt_normals=None,
                 override_alpha_thres=None, is_train=False, ndc_ray=False, N_samples=-1, tonemap=True, draw_debug=True,
                 max_weight_N=-1, noise=None):
+        if is_train and self._material_edit_table is not None:
+            raise ValueError("material edits are set: they are an evaluation feature and never enter a gradient "
+                             "(set_material_edits(None) before training)")
         if (recur == 0 and is_train and self.fused_training_pass and not self.regulariser_stats and rays.is_cuda
                 and torch.is_grad_enabled() and start_mipval is None and stepmul == 1 and override_near is None
                 and dynamic_batch_size and gt_normals is None and override_alpha_thres is None and not ndc_ray and N_samples == -1
@@ -224,7 +241,8 @@ class TensorNeRF(FastPrivateAttrs, torch.nn.Module):
         # Sparse appearance: the radiance only depends on the appearance features of the samples that spawn secondary
         # rays, so unless the per-sample debug maps are wanted (eval with draw_debug) the field's appearance branch and the
         # material heads run on those rows only (Microfacet.shade_compact).
-        dense_app = (not is_train) and draw_debug
+        # (material edits need the samples' heads where they are edited: the module path then evaluates them densely at every level)
+        dense_app = (not is_train) and (draw_debug or self._material_edit_table is not None)
         if M > 0 and hasattr(self.rf, "query_weights"):      # field query + raw2alpha as one graph node (:286,366,386,393)
             weight, _sf, app, world_normal = self.rf.query_weights(S.xyzt, S.dist, offsets, B, want_app=dense_app,
                                                                    want_normal=True)

@@ -46,7 +46,7 @@ import time
 
 import torch
 
-from . import synthetic
+from . import edit, synthetic
 from .modules.integral_equirect import IntegralEquirect
 from .modules.tensor_nerf import TensorNeRF
 from .noise import DeviceNoise
@@ -173,7 +173,12 @@ def main(argv=None):
     ap.add_argument("--panels", default="rgb,depth", help="panels of a --path frame, from rgb,depth,normal,acc (rgb always)")
     ap.add_argument("--animation", choices=("apng", "gif", "none"), default="apng",
                     help="container of the path's video.png / depthvideo.png (an animated PNG), .gif, or none")
+    edit.add_arguments(ap)
     args = ap.parse_args(argv)
+    try:
+        material_edits = edit.from_args(args)
+    except (edit.EditError, OSError) as e:
+        ap.error(str(e))
     if args.path:
         if not args.out:
             ap.error("--path needs --out (the frames go to OUT/path/)")
@@ -215,6 +220,7 @@ def main(argv=None):
         from . import relight
         nerf.bg_module = relight.rotate_env(nerf.bg_module, relight.rotation(*args.env_rotate))
     nerf.eval()
+    nerf.set_material_edits(material_edits)          # every mode below renders the edited materials
     chunk = args.chunk or nerf.eval_batch_size
     noise = DeviceNoise(dev, seed=11)
     render_frames(nerf, rays[:1, : min(chunk, rays.shape[1])], focal, chunk, noise)          # warm-up (table builds)

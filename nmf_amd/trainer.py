@@ -722,6 +722,9 @@ class Trainer:
         Returns a stats dict (python scalars)."""
         p = self.p
         nerf = self.nerf
+        if getattr(nerf, "_material_edit_table", None) is not None:
+            raise ValueError("material edits are set: they are an evaluation feature and never enter a gradient "
+                             "(nerf.set_material_edits(None) before training)")
         if self.world_size > 1 and self.check_every > 0 and self.iteration % self.check_every == 0 and _replica_group(None):
             check_replicas(nerf, what=f"before iteration {self.iteration}")
             self.replica_checks += 1
