@@ -830,6 +830,45 @@ int nmf_camera_rays(float r00, float r01, float r02, float r10, float r11, float
 int nmf_frame_finish(const float* rgb, const float* depth, const float* normal, const float* acc, float near, float far,
                      const uint8_t* lut, int32_t H, int32_t W, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Texture atlas of an exported mesh: one chart per triangle (nmf_amd/mesh.py:bake_textures; the reference exports
+ * no textures).  Not on the training path.  Added without a bump of NMF_ABI_VERSION: no earlier prototype or workspace size changed.
+ *
+ * Layout.  The atlas is W x W texels, 4 <= W <= 16384, texel t = y W + x with row y = 0 the top row of the picture.  It is cut into
+ * squares of T x T texels, n_sq = W / T (integer division) per row; square s = cy n_sq + cx holds face 2 s in its lower half and face
+ * 2 s + 1 in its upper half.  T >= 4 and n_sq^2 >= ceil(F / 2) (nmf_amd.mesh.atlas_layout picks the largest such T).  With the local
+ * texel (i, j) = (x - cx T, y - cy T) and b = T - 3: the lower face owns i + j <= T - 2 and has its corners 0, 1, 2 at (0, 0), (b, 0),
+ * (0, b); the upper face owns the rest and is the same under i' = T - 1 - i, j' = T - 1 - j.  Owned texels outside the triangle (the
+ * gutter a bilinear fetch inside the chart can reach) take the extrapolated barycentric point.  Unowned (face -1): squares past
+ * ceil(F / 2), the upper half of the last square of an odd F, the W - n_sq T left-over rows and columns.
+ *
+ * nmf_atlas_texels: for the texels t0 .. t0 + n - 1, face_of [n] int32 (the owning face or -1) and pos [n][3] fp32, the world point
+ *   of the texel on its face's plane; fp32, one rounding per operation, in this order (i, j: the local or the mirrored indices):
+ *     b1 = i / b,  b2 = j / b,  b0 = (1 - b1) - b2,  p_c = (b0 v0_c + b1 v1_c) + b2 v2_c.
+ *   verts [V][3] fp32, faces [F][3] int32.  Unowned texels get face -1 and position 0.  One launch, one lane per texel, closed form:
+ *   no atomics, no search; two runs give the same bytes.  Refused (nothing launched): a null pointer (verts / faces may be NULL when
+ *   F == 0), V or F below 0, W outside 4..16384, T below 4, above W or with (W / T)^2 < ceil(F / 2), n < 0, t0 < 0 or
+ *   t0 + n > W^2 (NMF_EINVAL); n == 0 launches nothing.  A face index outside [0, V) is a caller error (NMF_ERANGE in the
+ *   caller that can see the indices: they are device memory, so hip.atlas_texels reduces them once before the call); the kernel
+ *   checks every index against V before it reads verts, and the texels of such a face come out unowned.
+ *
+ * nmf_atlas_store: one chunk of baked attributes -> the byte planes of the atlas.  face_of [n], albedo [n][3], f0 [n][3],
+ *   roughness [n], normal [n][3] are indexed by t - t0; albedo_tex [W^2][3], f0_tex [W^2][3], rough_tex [W^2], normal_tex [W^2][3] by
+ *   t.  Per value a NaN counts as 0 before anything else; the casts truncate:
+ *     albedo     (uint8)(clamp(srgb(v), 0, 1) * 255), srgb(v) = v > 0.0031308 ? 1.055 pow(max(v, 0.0031308), 1 / 2.4) - 0.055 : 12.92 v
+ *     f0, rough  (uint8)(clamp(v, 0, 1) * 255)
+ *     normal     (uint8)clamp(v * 127 + 128, 0, 255)
+ *   Unowned texels (face_of < 0) are 0 0 0 / 0 0 0 / 0 / 128 128 128 and their inputs are not read.  A null plane is skipped (its
+ *   input may then be null too).  One launch; a lane owns the four texels of an aligned group and stores whole dwords where the group
+ *   lies inside [t0, t0 + n) and the plane is 4-byte aligned, bytes otherwise: nothing outside [t0, t0 + n) of a plane is written.
+ *   Refused (nothing launched): a null face_of, a plane without its input, W outside 4..16384, n < 0, t0 < 0 or t0 + n > W^2
+ *   (NMF_EINVAL). */
+int nmf_atlas_texels(const float* verts, const int32_t* faces, int64_t V, int64_t F, int32_t W, int32_t T, int64_t t0, int64_t n,
+                     float* pos, int32_t* face_of, void* stream);
+int nmf_atlas_store(const int32_t* face_of, const float* albedo, const float* f0, const float* roughness, const float* normal,
+                    int64_t t0, int64_t n, int32_t W, uint8_t* albedo_tex, uint8_t* f0_tex, uint8_t* rough_tex, uint8_t* normal_tex,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,7 @@ EXPORTS = [
     "nmf_relight_frame", "nmf_relight_ratio", "nmf_relight_ratio_workspace_bytes", "nmf_relight_adjust",
     "nmf_relight_adjust_workspace_bytes",
     "nmf_camera_rays", "nmf_frame_finish",
+    "nmf_atlas_texels", "nmf_atlas_store",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -1156,3 +1157,51 @@ def frame_finish(H, W, rgb=None, depth=None, normal=None, acc=None, near_far=(0.
         _check(_lib.nmf_frame_finish(*ptrs, float(near_far[0]), float(near_far[1]), _p(lut, torch.uint8), H, W, _p(out, torch.uint8),
                                      _stream()), "nmf_frame_finish")
     return out.view(H, n * W, 3)
+
+
+# ---- texture atlas of an exported mesh (csrc/atlas.hip; nmf_amd/mesh.py:bake_textures) ----------------------------------------------
+def atlas_texels(verts, faces, W, T, t0=0, n=None, check_faces=True, out=None):
+    """nmf_atlas_texels: the owning face (int32 [n], -1: none) and the world position (fp32 [n, 3]) of the texels t0 .. t0 + n - 1 of
+    the W x W atlas with T x T squares over the mesh verts fp32 [V, 3], faces int32 [F, 3] (layout: include/nmf_hip.h,
+    nmf_amd.mesh.atlas_layout).  n None: to the end of the atlas.  check_faces: one min / max reduction of the indices first; an
+    index outside [0, V) is refused (NMF_ERANGE) before anything is written -- a caller that walks the atlas in chunks checks once.
+    out: the (pos, face_of) tensors to fill.  -> (pos, face_of)"""
+    vp, fp = _p(verts, torch.float32), _p(faces, torch.int32)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise NmfHipError(f"atlas_texels: verts [V, 3] and faces [F, 3] on one device, got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    W, T, t0 = int(W), int(T), int(t0)
+    n = W * W - t0 if n is None else int(n)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if check_faces and F > 0:
+        lo, hi = (int(v) for v in torch.stack([faces.min(), faces.max()]).tolist())
+        if lo < 0 or hi >= V:
+            raise NmfHipError(f"nmf_atlas_texels failed: face indices {lo}..{hi} leave [0, {V}) [-2]")
+    if out is None:
+        out = (torch.empty((max(n, 0), 3), dtype=torch.float32, device=verts.device),
+               torch.empty((max(n, 0),), dtype=torch.int32, device=verts.device))
+    pos, face_of = out
+    if pos.numel() != 3 * max(n, 0) or face_of.numel() != max(n, 0) or pos.device != verts.device or face_of.device != verts.device:
+        raise NmfHipError(f"atlas_texels: out holds {pos.numel()} and {face_of.numel()} values, {n} texels need {3 * n} and {n}")
+    with torch.cuda.device(verts.device):
+        _check(_lib.nmf_atlas_texels(vp, fp, V, F, W, T, t0, n, _p(pos), _p(face_of), _stream()), "nmf_atlas_texels")
+    return pos, face_of
+
+
+def atlas_store(face_of, albedo, f0, roughness, normal, t0, W, albedo_tex=None, f0_tex=None, rough_tex=None, normal_tex=None):
+    """nmf_atlas_store: the attributes of the texels t0 .. t0 + n - 1 (face_of int32 [n]; albedo, f0, normal fp32 [n, 3], roughness
+    fp32 [n]; the input of a plane that is None may be None) quantised IN PLACE into the uint8 planes of the W x W atlas: albedo_tex,
+    f0_tex, normal_tex [W, W, 3], rough_tex [W, W] (include/nmf_hip.h: sRGB albedo, linear f0 and roughness, 127 v + 128 normals;
+    unowned texels get the fill values).  A plane that is None is skipped."""
+    n, W, t0 = int(face_of.numel()), int(W), int(t0)
+    ptrs = [_p(face_of, torch.int32)]
+    for name, t, c in (("albedo", albedo, 3), ("f0", f0, 3), ("roughness", roughness, 1), ("normal", normal, 3)):
+        if t is not None and (t.numel() != c * n or t.device != face_of.device):
+            raise NmfHipError(f"atlas_store: {name} holds {t.numel()} values on {t.device}, {n} texels need {c * n}")
+        ptrs.append(_p(t, torch.float32))
+    planes = []
+    for name, t, c in (("albedo_tex", albedo_tex, 3), ("f0_tex", f0_tex, 3), ("rough_tex", rough_tex, 1), ("normal_tex", normal_tex, 3)):
+        if t is not None and (t.numel() != c * W * W or t.device != face_of.device):
+            raise NmfHipError(f"atlas_store: {name} holds {t.numel()} bytes on {t.device}, a {W} x {W} atlas needs {c * W * W}")
+        planes.append(_p(t, torch.uint8))
+    with torch.cuda.device(face_of.device):
+        _check(_lib.nmf_atlas_store(*ptrs, t0, n, W, *planes, _stream()), "nmf_atlas_store")

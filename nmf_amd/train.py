@@ -25,7 +25,8 @@ Prints one JSON line per evaluation: iteration, train PSNR proxy (train.py:609-6
 8-bit formula (renderer.py:399-401), rays/s.  --render-test (Blender scenes, train.py:861-875): after training, rank 0 evaluates
 every test view (renderer.evaluation: PSNR, SSIM, normal error, frames) into <logfolder>/imgs_test_all/ and prints one more line
 {"test_all": {"psnr", "ssim", "norm_err", "views"}}.  --export-mesh: after training, rank 0 writes the alpha iso-surface with
-per-vertex normals and materials to <logfolder>/<expname>.ply (nmf_amd.export_mesh) and prints {"mesh": {"V", "F", "seconds", ...}}.
+per-vertex normals and materials to <logfolder>/<expname>.ply (nmf_amd.export_mesh) and prints {"mesh": {"V", "F", "seconds", ...}};
+with --texture-size W the materials and normals are baked into a W x W texture atlas and <expname>.obj + .mtl + PNGs are written.
 """
 import argparse
 import json
@@ -121,12 +122,17 @@ def main(argv=None):
                          "<logfolder>/imgs_path_all/ (train.py:884-901); the override render_path=True does the same")
     ap.add_argument("--export-mesh", action="store_true",
                     help="after training: marching cubes of the alpha lattice into <logfolder>/<expname>.ply (nmf_amd.export_mesh)")
+    ap.add_argument("--texture-size", type=int, default=None, metavar="W",
+                    help="with --export-mesh: bake the materials and normals into a W x W texture atlas and write "
+                         "<logfolder>/<expname>.obj + .mtl + PNGs instead of the PLY")
     ap.add_argument("-m", "--multirun", action="store_true",
                     help="hydra multirun (README.md:10): comma-separated override values span a sweep, run job by job")
     ap.add_argument("overrides", nargs="*", help="hydra-style tokens: group=name, a.b.c=value")
     args = ap.parse_args(argv)
     if args.material_maps and not args.render_test:
         ap.error("--material-maps needs --render-test")
+    if args.texture_size is not None and not args.export_mesh:
+        ap.error("--texture-size needs --export-mesh")
     for o in args.overrides:
         if "=" not in o:
             ap.error(f"'{o}': overrides are key=value tokens (hydra syntax)")
@@ -305,7 +311,8 @@ def main(argv=None):
         from .export_mesh import export
         os.makedirs(logfolder, exist_ok=True)
         nerf.eval()
-        print(json.dumps(dict(mesh=export(nerf, os.path.join(logfolder, f"{expname}.ply")))), flush=True)
+        ext = ".ply" if args.texture_size is None else ".obj"
+        print(json.dumps(dict(mesh=export(nerf, os.path.join(logfolder, expname + ext), texture_size=args.texture_size))), flush=True)
     if world > 1:
         dist.destroy_process_group()
     return cfg
