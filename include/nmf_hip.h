@@ -869,6 +869,54 @@ int nmf_atlas_store(const int32_t* face_of, const float* albedo, const float* f0
                     int64_t t0, int64_t n, int32_t W, uint8_t* albedo_tex, uint8_t* f0_tex, uint8_t* rough_tex, uint8_t* normal_tex,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scene composition: several trained objects under one environment (nmf_amd/compose.py, csrc/compose.hip; the
+ * reference's scripts/toaster_on_car.py over fields/listrf.py).  Not on the training path.  Added without a bump of
+ * NMF_ABI_VERSION: no earlier prototype or workspace size changed.
+ *
+ * A placement maps an object's frame to the world: x_w = s R x_l + c, R [9] row-major rotation and c [3] HOST pointers, s > 0.
+ *
+ * nmf_rays_place: rays [B][6] = origin | direction between the two frames, one lane per ray; fp32, one rounding per operation:
+ *     inverse = 1 (world -> local):  t = o - c,  o'_i = ((R_0i t_0 + R_1i t_1) + R_2i t_2) / s,  d'_i = (R_0i d_0 + R_1i d_1) + R_2i d_2
+ *     inverse = 0 (local -> world):  o'_i = s ((R_i0 o_0 + R_i1 o_1) + R_i2 o_2) + c_i,          d'_i = (R_i0 d_0 + R_i1 d_1) + R_i2 d_2
+ *   Directions are rotated only, never renormalised.  With R = I, c = 0, s = 1 exactly the rows are copied (the input's bits, a
+ *   -0 included).  rays_out may be rays_in.  Refused (nothing launched): a null pointer (rays may be null when B == 0), B < 0, s or
+ *   c not finite, s <= 0, inverse other than 0 / 1, max|R^T R - I| > 1e-4 (NMF_EINVAL).
+ *
+ * nmf_merge_rank: K lists of per-ray samples (CSR offsets [B+1] int64 over the same B rays, depths z [M_k] fp32 non-decreasing
+ *   inside a ray, a positive scale each) -> the place dst_k [M_k] int64 of every sample in the merged list and its offsets
+ *   offsets_m [B+1] = sum_k offsets_k.  The merged list of a ray is the stable K-way merge by world depth scale_k z: ascending
+ *   depth, ties by list index, then by original order, i.e. the rank of a sample is its own index in its segment plus, per other
+ *   list j, the number of entries with scale_j z_j < scale_k z, or equal and j < k (binary search).  One lane per sample, one
+ *   launch, no atomics: two runs give the same bytes.  Lists with M_k == 0 and rays that are empty in every list are valid.  Every
+ *   offset is clamped to [0, M_k] and every rank to its ray's merged segment before use.  Refused (nothing launched): K outside
+ *   1..NMF_MERGE_MAX_LISTS (NMF_ERANGE); a null lists, offsets_m or offsets_k, a null z_k or dst_k where M_k > 0, M_k < 0, B < 0,
+ *   samples with B == 0, a scale that is not finite and positive (NMF_EINVAL).
+ *
+ * nmf_merge_scatter: the rows of ONE list written to their places, one lane per sample; an output that is NULL is skipped (its
+ *   input may then be NULL): sigma_m[d] = sigma[i] sigma_ratio, dist_m[d] = dist[i], z_m[d] = scale z[i],
+ *   normal_m[d]_c = (R_c0 n_0 + R_c1 n_1) + R_c2 n_2, ray_id_m[d] = ray_id[i], part_m[d] = part, src_m[d] = i,
+ *   inv_m[d] = inv[i] >= 0 ? inv[i] + row_base : -1, with d = dst[i]; a d outside [0, M_total) writes nothing.  The bounce-row map
+ *   inv exists only after the list was shaded with the merged weights, so a caller scatters twice: the geometry before compositing,
+ *   inv_m after shading.  Refused (nothing launched): M_k < 0, M_total < M_k, a null dst with M_k > 0, an output without its input,
+ *   sigma_ratio or scale not finite and positive, normal_m with a null R or max|R^T R - I| > 1e-4 (NMF_EINVAL); part outside
+ *   0..NMF_MERGE_MAX_LISTS - 1, M_k or row_base above 2^31 - 1 (NMF_ERANGE). */
+#define NMF_MERGE_MAX_LISTS 8
+typedef struct {
+    const int64_t* offsets[NMF_MERGE_MAX_LISTS];   /* device [B+1] */
+    const float* z[NMF_MERGE_MAX_LISTS];           /* device [M_k] */
+    int64_t* dst[NMF_MERGE_MAX_LISTS];             /* device [M_k], written */
+    float scale[NMF_MERGE_MAX_LISTS];
+    int64_t M[NMF_MERGE_MAX_LISTS];
+} nmf_merge_lists;
+int nmf_rays_place(const float* rays_in, const float* R, const float* c, float s, int32_t inverse, int64_t B, float* rays_out,
+                   void* stream);
+int nmf_merge_rank(int32_t K, const nmf_merge_lists* lists, int64_t B, int64_t* offsets_m, void* stream);
+int nmf_merge_scatter(int64_t M_k, int64_t M_total, const int64_t* dst, const float* sigma, const float* dist, const float* z,
+                      const float* normal, const int32_t* ray_id, const int32_t* inv, float sigma_ratio, float scale, const float* R,
+                      int32_t part, int64_t row_base, float* sigma_m, float* dist_m, float* z_m, float* normal_m, int32_t* ray_id_m,
+                      int32_t* part_m, int32_t* src_m, int32_t* inv_m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

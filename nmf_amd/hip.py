@@ -102,6 +102,7 @@ EXPORTS = [
     "nmf_relight_adjust_workspace_bytes",
     "nmf_camera_rays", "nmf_frame_finish",
     "nmf_atlas_texels", "nmf_atlas_store",
+    "nmf_rays_place", "nmf_merge_rank", "nmf_merge_scatter",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -1205,3 +1206,93 @@ def atlas_store(face_of, albedo, f0, roughness, normal, t0, W, albedo_tex=None, 
         planes.append(_p(t, torch.uint8))
     with torch.cuda.device(face_of.device):
         _check(_lib.nmf_atlas_store(*ptrs, t0, n, W, *planes, _stream()), "nmf_atlas_store")
+
+
+# ---- scene composition (csrc/compose.hip; nmf_amd/compose.py) -------------------------------------------------------------------------
+MERGE_MAX_LISTS = 8
+
+
+class MergeLists(C.Structure):
+    _fields_ = [("offsets", C.c_void_p * MERGE_MAX_LISTS), ("z", C.c_void_p * MERGE_MAX_LISTS), ("dst", C.c_void_p * MERGE_MAX_LISTS),
+                ("scale", C.c_float * MERGE_MAX_LISTS), ("M", C.c_int64 * MERGE_MAX_LISTS)]
+
+
+def _placement_args(R, c, s):
+    """host float32 blocks of a placement x_w = s R x_l + c; R may be an object with .R, .t and .s (nmf_amd.compose.Placement)"""
+    if hasattr(R, "R") and hasattr(R, "t") and hasattr(R, "s"):
+        R, c, s = R.R, R.t, R.s
+    r = np.asarray(R, dtype=np.float64).reshape(-1)
+    t = np.zeros(3) if c is None else np.asarray(c, dtype=np.float64).reshape(-1)
+    if r.size != 9 or t.size != 3:
+        raise NmfHipError("a placement has a 3x3 rotation and a translation of 3")
+    return (C.c_float * 9)(*[float(v) for v in r]), (C.c_float * 3)(*[float(v) for v in t]), float(np.float32(s))
+
+
+def rays_place(rays, R, c=None, s=1.0, inverse=False, out=None):
+    """nmf_rays_place: rays fp32 [B, 6] (origin | direction) between the world and an object's frame under the placement
+    x_w = s R x_l + c (R 3x3, c 3, s: host numbers, or R a nmf_amd.compose.Placement).  inverse: world -> local, o' = R^T (o - c) / s,
+    d' = R^T d; otherwise local -> world, o' = s R o + c, d' = R d.  Directions are not renormalised.  -> out (a new tensor, or
+    `out`, which may be `rays`)"""
+    if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+        raise NmfHipError(f"rays_place: rays are [B, 6], got {tuple(getattr(rays, 'shape', ()))}")
+    rp = _p(rays, torch.float32)
+    if out is None:
+        out = torch.empty_like(rays)
+    if out.shape != rays.shape or out.device != rays.device:
+        raise NmfHipError("rays_place: out must have the shape and device of rays")
+    Rc, cc, sc = _placement_args(R, c, s)
+    with torch.cuda.device(rays.device):
+        _check(_lib.nmf_rays_place(rp, Rc, cc, sc, 1 if inverse else 0, int(rays.shape[0]), _p(out, torch.float32), _stream()),
+               "nmf_rays_place")
+    return out
+
+
+def merge_rank(offsets, zs, scales, B):
+    """nmf_merge_rank: K <= 8 per-ray sample lists over the same B rays (offsets[k] int64 [>= B+1], zs[k] fp32 [M_k] non-decreasing
+    inside a ray, scales[k] > 0) -> (dst: a list of int64 [M_k], the place of every sample in the list merged by world depth
+    scales[k] * zs[k] -- stable: ties by list index, then by original order --, offsets_m int64 [B+1])"""
+    K, B = len(offsets), int(B)
+    if len(zs) != K or len(scales) != K:
+        raise NmfHipError("merge_rank: offsets, zs and scales are lists of one length")
+    L = MergeLists()
+    dst = []
+    dev = offsets[0].device if K else torch.device("cuda")
+    for k in range(min(K, MERGE_MAX_LISTS)):
+        if offsets[k].numel() < B + 1 or zs[k].dim() != 1 or offsets[k].device != dev or zs[k].device != dev:
+            raise NmfHipError(f"merge_rank: list {k} needs offsets of B + 1 = {B + 1} entries and a 1-d z on one device")
+        d = torch.empty(zs[k].shape[0], dtype=torch.int64, device=dev)
+        dst.append(d)
+        L.offsets[k], L.z[k], L.dst[k] = _p(offsets[k], torch.int64), _p(zs[k], torch.float32), _p(d)
+        L.scale[k], L.M[k] = float(scales[k]), int(zs[k].shape[0])
+    offsets_m = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(_lib.nmf_merge_rank(K, C.byref(L), B, _p(offsets_m), _stream()), "nmf_merge_rank")
+    return dst, offsets_m
+
+
+def merge_scatter(dst, M_total, part=0, sigma=None, dist=None, z=None, normal=None, ray_id=None, inv=None, sigma_ratio=1.0, scale=1.0,
+                  R=None, row_base=0, out=None):
+    """nmf_merge_scatter: the rows of one list written IN PLACE to their places dst int64 [M_k] in the merged arrays
+    out = dict(sigma, dist, z fp32 [M_total]; normal fp32 [M_total, 3]; ray_id, part, src, inv int32 [M_total]): every array present in
+    `out` is written (sigma * sigma_ratio, dist, scale * z, R normal, ray_id, part, the row's index, inv + row_base or -1) and needs
+    its input.  -> out"""
+    out = out or {}
+    M_k, M_total = int(dst.shape[0]), int(M_total)
+    for name, t, c in (("sigma", sigma, 1), ("dist", dist, 1), ("z", z, 1), ("normal", normal, 3), ("ray_id", ray_id, 1), ("inv", inv, 1)):
+        if t is not None and (t.numel() != c * M_k or t.device != dst.device):
+            raise NmfHipError(f"merge_scatter: {name} holds {t.numel()} values on {t.device}, {M_k} rows need {c * M_k}")
+    for name, t in out.items():
+        c = 3 if name == "normal" else 1
+        if name not in ("sigma", "dist", "z", "normal", "ray_id", "part", "src", "inv"):
+            raise NmfHipError(f"merge_scatter: unknown output '{name}'")
+        if t.numel() != c * M_total or t.device != dst.device:
+            raise NmfHipError(f"merge_scatter: out['{name}'] holds {t.numel()} values on {t.device}, {M_total} rows need {c * M_total}")
+    f, i = torch.float32, torch.int32
+    Rc = _placement_args(R, None, 1.0)[0] if R is not None else None
+    o = out.get
+    with torch.cuda.device(dst.device):
+        _check(_lib.nmf_merge_scatter(M_k, M_total, _p(dst, torch.int64), _p(sigma, f), _p(dist, f), _p(z, f), _p(normal, f), _p(ray_id, i),
+                                      _p(inv, i), float(sigma_ratio), float(scale), Rc, int(part), int(row_base), _p(o("sigma"), f),
+                                      _p(o("dist"), f), _p(o("z"), f), _p(o("normal"), f), _p(o("ray_id"), i), _p(o("part"), i),
+                                      _p(o("src"), i), _p(o("inv"), i), _stream()), "nmf_merge_scatter")
+    return out

@@ -38,12 +38,22 @@ train.py:884-901) renders views that are in no data set into OUT/path/: --frames
 --datadir: a --res square camera, radius 4, elevation 30 degrees) or the poses of a transforms file; {k:03d}.png, depth/,
 world_normal/, acc_map/ per --panels, video.png / depthvideo.png (animated PNGs at --fps; --animation gif|none) and
 transforms_path.json.  Rays and 8-bit frames are made on the device; PNGs are encoded on a writer thread.  The line gains `path`.
+
+    python -m nmf_amd.render --ckpt log/car.th --insert 'log/toaster.th@t=0,0,0.9;r=40,0,0;s=0.4' --path orbit --out imgs/
+
+--insert 'CKPT[@SPEC]' (repeatable; nmf_amd/compose.py; the reference's scripts/toaster_on_car.py) puts further trained
+objects into the scene of --ckpt, which --place SPEC moves itself: the objects occlude, shadow and reflect each other under ONE
+environment (the --ckpt model's own, carried along with it, or the --fixed-bg / --env-rotate one).  SPEC is t=x,y,z;r=yaw,pitch,roll;s=scale
+(local -> world, degrees, +z up; any subset).  --near-far is then in world units, and without it every object is marched over the range
+its box limits.  Works with --views, --path, --panels, --fixed-bg, --env-rotate and --light-turntable; orbit and spiral paths circle
+the box around all objects.  The line gains `parts` and `placements`.
 """
 import argparse
 import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import edit, synthetic
@@ -112,6 +122,11 @@ def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None):
     return dict(light_frames=n, light_env_seconds=env_s, light_render_seconds=render_s)
 
 
+def _model_aabb(nerf):
+    from . import hip
+    return hip.host(nerf.rf.aabb).astype(np.float64).reshape(2, 3)
+
+
 def render_path(nerf, args, ds, near_far, panels, noise, dev):
     """--path: the poses (nmf_amd/camera_path.py) and the camera, rendered by renderer.evaluation_path into <out>/path/ under the
     lighting the command set up (--fixed-bg, --env-rotate, --bg-res).  Without a data set the camera is --res square with the
@@ -128,10 +143,18 @@ def render_path(nerf, args, ds, near_far, panels, noise, dev):
     if args.path in ("orbit", "spiral", "interp"):
         if ds is not None:
             c2ws = camera_path.from_dataset(ds, args.path, args.frames)
-        elif args.path == "orbit":
-            c2ws = camera_path.orbit(args.frames, (0.0, 0.0, 0.0), 4.0, 30.0)
         else:
-            c2ws = camera_path.spiral(args.frames, (0.0, 0.0, 0.0), 4.0, (15.0, 45.0))
+            center, radius = (0.0, 0.0, 0.0), 4.0
+            if hasattr(nerf, "world_aabb"):
+                # a composed scene: around the box of all objects, at the distance that shows it as radius 4 shows one object
+                box = nerf.world_aabb()
+                own = _model_aabb(nerf.parts[0][0])
+                center = tuple(float(v) for v in 0.5 * (box[0] + box[1]))
+                radius = 4.0 * max(float(np.linalg.norm(box[1] - box[0]) / np.linalg.norm(own[1] - own[0])), 1.0)
+            if args.path == "orbit":
+                c2ws = camera_path.orbit(args.frames, center, radius, 30.0)
+            else:
+                c2ws = camera_path.spiral(args.frames, center, radius, (15.0, 45.0))
     else:
         c2ws, camera = camera_path.load_path(args.path, with_camera=True)
         if "near_far" not in json.load(open(args.path)):
@@ -147,7 +170,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", required=True)
     ap.add_argument("--datadir", default=None)
-    ap.add_argument("--near-far", type=float, nargs=2, default=[2.5, 7.0])
+    ap.add_argument("--near-far", type=float, nargs=2, default=None,
+                    help="near and far plane of the synthetic cameras (default 2.5 7.0; with --insert / --place: world units, default: "
+                         "every object over the range its box limits)")
     ap.add_argument("--fixed-bg", default=None)
     ap.add_argument("--out", default=None, help="directory for PNG frames")
     ap.add_argument("--views", type=int, default=2)
@@ -173,8 +198,36 @@ def main(argv=None):
     ap.add_argument("--panels", default="rgb,depth", help="panels of a --path frame, from rgb,depth,normal,acc (rgb always)")
     ap.add_argument("--animation", choices=("apng", "gif", "none"), default="apng",
                     help="container of the path's video.png / depthvideo.png (an animated PNG), .gif, or none")
+    ap.add_argument("--insert", action="append", default=[], metavar="CKPT[@SPEC]",
+                    help="a further trained object in the scene, repeatable: a checkpoint and its placement "
+                         "'t=x,y,z;r=yaw,pitch,roll;s=scale' (local -> world, degrees, +z up; any subset; default: the identity)")
+    ap.add_argument("--place", default=None, metavar="SPEC", help="the placement of the --ckpt model itself in a composed scene")
     edit.add_arguments(ap)
     args = ap.parse_args(argv)
+    composed = bool(args.insert) or args.place is not None
+    placements = None
+    if composed:
+        from .compose import Placement
+        for flag, given in (("--eval-dir", args.eval_dir), ("--relight-eval", args.relight_eval), ("--material-maps", args.material_maps),
+                            ("--edit", args.edit or args.edit_file)):
+            if given:
+                ap.error(f"{flag} is not built for a composed scene (--insert / --place)")
+        if len(args.insert) > 7:
+            ap.error("--insert: a composed scene has at most 8 objects")
+        try:
+            placements = [Placement.from_spec(args.place or "")]
+            inserts = []
+            for item in args.insert:
+                ckpt, _, spec = item.partition("@")
+                if not ckpt:
+                    ap.error(f"--insert '{item}': no checkpoint")
+                inserts.append(ckpt)
+                placements.append(Placement.from_spec(spec))
+        except ValueError as e:
+            ap.error(f"--insert / --place: {e}")
+    explicit_near_far = args.near_far is not None
+    if args.near_far is None:
+        args.near_far = [2.5, 7.0]
     try:
         material_edits = edit.from_args(args)
     except (edit.EditError, OSError) as e:
@@ -214,19 +267,26 @@ def main(argv=None):
         r, focal = synthetic.orbit_rays(args.views, args.res, seed=2)
         rays, near_far, wh = r.reshape(args.views, -1, 6).to(dev), tuple(args.near_far), [args.res, args.res]
     nerf = TensorNeRF.load(args.ckpt, near_far=list(near_far), device=dev)
+    if composed:
+        from .compose import ComposedScene
+        models = [nerf.eval()] + [TensorNeRF.load(c, near_far=list(near_far), device=dev).eval() for c in inserts]
+        nerf = ComposedScene(list(zip(models, placements)), near_far=tuple(args.near_far) if explicit_near_far else None)
     if args.fixed_bg:
         nerf.bg_module = load_fixed_bg(args.fixed_bg, dev, args.bg_res)
     if args.env_rotate is not None:
         from . import relight
         nerf.bg_module = relight.rotate_env(nerf.bg_module, relight.rotation(*args.env_rotate))
     nerf.eval()
-    nerf.set_material_edits(material_edits)          # every mode below renders the edited materials
+    if not composed:
+        nerf.set_material_edits(material_edits)          # every mode below renders the edited materials
     chunk = args.chunk or nerf.eval_batch_size
     noise = DeviceNoise(dev, seed=11)
     render_frames(nerf, rays[:1, : min(chunk, rays.shape[1])], focal, chunk, noise)          # warm-up (table builds)
     rgb, dt = render_frames(nerf, rays, focal, chunk, noise)
     rec = dict(frames=int(rays.shape[0]), width=wh[0], height=wh[1], chunk=chunk, seconds=round(dt, 4),
                rays_per_s=round(rays.shape[0] * rays.shape[1] / dt, 1), relit=bool(args.fixed_bg))
+    if composed:
+        rec.update(parts=len(placements), placements=[p.spec() for p in placements])
     if gt is not None:
         rec["psnr"] = round(float(torch.stack([psnr_8bit(rgb[i], gt[i]) for i in range(rgb.shape[0])]).mean()), 3)
     if args.out:
