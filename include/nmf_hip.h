@@ -917,6 +917,67 @@ int nmf_merge_scatter(int64_t M_k, int64_t M_total, const int64_t* dst, const fl
                       int32_t part, int64_t row_base, float* sigma_m, float* dist_m, float* z_m, float* normal_m, int32_t* ray_id_m,
                       int32_t* part_m, int32_t* src_m, int32_t* inv_m, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-sample frames: per-pixel accumulation of several passes and adaptive sample counts (nmf_amd/multisample.py:render_frame,
+ * csrc/accum.hip; the reference renders one sample per pixel).  Not on the training path.  Added without a bump of
+ * NMF_ABI_VERSION: no earlier prototype or workspace size changed.
+ *
+ * A frame has P = H W pixels, pixel p = row W + col.  A pixel list pix [n] is int32, strictly ascending; a NULL pix stands for all P
+ * pixels in order (n is then not used; an empty list is a non-NULL pix with n = 0).  Per-pass arrays are indexed by the list entry i, the state and the finished maps by the
+ * pixel.  Every kernel is one lane per pixel or list entry with plain loads and stores; every id read from a list is checked against
+ * [0, P) before it indexes anything, and an entry outside is skipped.  Two runs give the same bytes.
+ *
+ * State.  nmf_accum_state_bytes(H, W) bytes (0 for a frame that would be refused), 4-byte aligned, allocated and ZEROED by the caller:
+ * NMF_ACCUM_PLANES planes of P 4-byte words, plane k of pixel p at word k P + p --
+ *     0 count (int32) | 1-3 mean rgb_lin | 4 mean acc | 5 mean depth | 6-8 mean normal | 9-11 mean rgb_map | 12-14 M2 of rgb_map
+ * (fp32; M2 is the sum of squared deviations per channel), then one int32 per tile of NMF_ACCUM_TILE pixels, scratch of
+ * nmf_accum_active.
+ *
+ * nmf_camera_rays_at: rays [n][6] (or [P][6] for a NULL list), row i the ray of pixel pix[i] through the point (col + ox, row + oy):
+ *     x = ((col + ox) - cx) / fx,  y = ((row + oy) - cy) / fy, the rest as nmf_camera_rays, same order of operations.
+ *   seed == 0: (ox, oy) = (jx, jy).  Otherwise a per-pixel rotation in [0, 1)^2 is added and wrapped, in uint32 arithmetic:
+ *     mix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *     h0 = mix(p 0x9E3779B1 + seed 0x85EBCA77),  h1 = mix(h0 + 0x9E3779B9),  u_k = (float)(h_k >> 8) 2^-24
+ *     ox = jx + u_0; if (ox >= 1) ox = ox - 1;   oy likewise from jy and u_1            (fp32, one rounding per operation)
+ *   jx = jy = 0.5, seed = 0 and a NULL list give the bytes of nmf_camera_rays.  Rows of skipped entries keep what they held.
+ *   Refused (nothing launched): as nmf_camera_rays, and n < 0 or jx / jy outside [0, 1] (NMF_EINVAL), n above 2^31 - 1 (NMF_ERANGE);
+ *   an empty list launches nothing.
+ *
+ * nmf_accum_update: folds one pass into the state for the pixels of the list.  rgb_lin [n][3], acc [n], rgb_map [n][3] (the
+ *   displayed colour the pass formed), optionally depth [n] and normal [n][3] (NULL: those means are left alone).  Per pixel and
+ *   value x (a NaN counts as 0), Welford's update, fp32, one rounding per operation:
+ *     count += 1;  d = x - mean;  mean = mean + d / count;  and for rgb_map  M2 = M2 + d (x - mean).
+ *   After one sample the means are the sample's bits.  A list that names a pixel twice is a caller error (the result is one of the
+ *   two updates, nothing is written elsewhere).  Refused: H or W below 1, n < 0, a NULL state, rgb_lin, acc or rgb_map with n > 0,
+ *   a misaligned state (NMF_EINVAL); H W or n above 2^31 - 1 (NMF_ERANGE).
+ *
+ * nmf_accum_active: list [<= P] = the ascending ids of the pixels that still need samples, *n_out (device int32) their number.  With
+ *     se = max_c sqrt(M2_c / ((float)count (float)(count - 1)))  for count >= 2, else 0                  (display units)
+ *   pixel p is active when count < min_spp, or count < max_spp and se > tol.  Three launches on the stream: the count of active pixels
+ *   per tile, ONE workgroup that turns the tile counts into exclusive sums (and writes *n_out), and a second pass over the pixels
+ *   that stores each active id at its tile's offset plus its rank inside the tile (ballots).  No atomics: the list is
+ *   np.flatnonzero of the predicate.  Entries of list past *n_out are not written.  Refused: H or W below 1, min_spp < 0,
+ *   max_spp < min_spp, tol negative or a NaN (+inf is allowed), a NULL or misaligned pointer (NMF_EINVAL); H W above 2^31 - 1
+ *   (NMF_ERANGE).
+ *
+ * nmf_accum_resolve: the finished maps, each may be NULL: rgb_map [P][3] = (tonemap ? srgb(mean rgb_lin) : mean rgb_lin) +
+ *   (1 - mean acc) bg with nmf_ray_compose_fwd's srgb and flags (the power taken in double and rounded to fp32 once); acc [P],
+ *   depth [P], normal [P][3] the plain means (not renormalised: one sample gives the pass's own maps); se [P] as above; count [P] as
+ *   float.  The average is taken on linear radiance and tonemapped afterwards; se is that of the displayed colour.  Refused: H or W
+ *   below 1, a bg that is not finite, a NULL state, all six outputs NULL (NMF_EINVAL); H W above 2^31 - 1 (NMF_ERANGE). */
+#define NMF_ACCUM_PLANES 15
+#define NMF_ACCUM_TILE 256
+int64_t nmf_accum_state_bytes(int32_t H, int32_t W);
+int nmf_camera_rays_at(float r00, float r01, float r02, float r10, float r11, float r12, float r20, float r21, float r22, float tx,
+                       float ty, float tz, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float jx, float jy,
+                       uint32_t seed, const int32_t* pix, int64_t n, float* rays, void* stream);
+int nmf_accum_update(void* state, int32_t H, int32_t W, const int32_t* pix, int64_t n, const float* rgb_lin, const float* acc,
+                     const float* rgb_map, const float* depth, const float* normal, void* stream);
+int nmf_accum_active(void* state, int32_t H, int32_t W, int32_t min_spp, int32_t max_spp, float tol, int32_t* list, int32_t* n_out,
+                     void* stream);
+int nmf_accum_resolve(const void* state, int32_t H, int32_t W, float bg_r, float bg_g, float bg_b, int32_t tonemap, int32_t noclip,
+                      float* rgb_map, float* acc, float* depth, float* normal, float* se, float* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,7 @@ EXPORTS = [
     "nmf_camera_rays", "nmf_frame_finish",
     "nmf_atlas_texels", "nmf_atlas_store",
     "nmf_rays_place", "nmf_merge_rank", "nmf_merge_scatter",
+    "nmf_accum_state_bytes", "nmf_camera_rays_at", "nmf_accum_update", "nmf_accum_active", "nmf_accum_resolve",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -1295,4 +1296,109 @@ def merge_scatter(dst, M_total, part=0, sigma=None, dist=None, z=None, normal=No
                                       _p(inv, i), float(sigma_ratio), float(scale), Rc, int(part), int(row_base), _p(o("sigma"), f),
                                       _p(o("dist"), f), _p(o("z"), f), _p(o("normal"), f), _p(o("ray_id"), i), _p(o("part"), i),
                                       _p(o("src"), i), _p(o("inv"), i), _stream()), "nmf_merge_scatter")
+    return out
+
+
+# ---- multi-sample frames: rays of a pixel list, per-pixel accumulation, the active list (csrc/accum.hip; nmf_amd/multisample.py) ------
+ACCUM_PLANES, ACCUM_TILE = 15, 256          # NMF_ACCUM_PLANES, NMF_ACCUM_TILE of include/nmf_hip.h
+
+
+def accum_state_bytes(H, W):
+    """nmf_accum_state_bytes: the bytes of the per-pixel state of an H x W frame (host arithmetic)"""
+    n = int(_lib.nmf_accum_state_bytes(int(H), int(W)))
+    if n <= 0:
+        raise NmfHipError(f"accum_state_bytes: a frame is at least 1 x 1 and at most 2^31 - 1 pixels, got {H} x {W}")
+    return n
+
+
+def _pixel_list(pix, what, device):
+    if pix is None:
+        return None, 0
+    if pix.dtype != torch.int32 or pix.dim() != 1 or not pix.is_cuda or pix.device != device:
+        raise NmfHipError(f"{what}: pix is a 1-d int32 tensor on the device of the frame")
+    return pix, int(pix.shape[0])
+
+
+def camera_rays_at(c2w, fx, fy, cx, cy, H, W, jitter=(0.5, 0.5), seed=0, pix=None, device="cuda", out=None):
+    """nmf_camera_rays_at: the rays of the pixels pix (int32, ascending; None: all H W) of camera_rays' camera through the point
+    jitter = (jx, jy) in [0, 1]^2 of each pixel, rotated per pixel by the hash of (pixel, seed) when seed != 0 (include/nmf_hip.h).
+    -> fp32 [n, 6] (out: a device tensor of at least 6 n values whose first n rows are filled and returned)"""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise NmfHipError(f"camera_rays_at: H and W are at least 1, got {H} x {W}")
+    device = out.device if out is not None else (pix.device if pix is not None else torch.device(device))
+    if torch.device(device).type != "cuda":
+        raise NmfHipError("camera_rays_at: nmf_amd operators need device tensors (no CPU path)")
+    pix, n = _pixel_list(pix, "camera_rays_at", device)
+    rows = H * W if pix is None else n
+    if out is None:
+        out = torch.empty((rows, 6), dtype=torch.float32, device=device)
+    ptr = _p(out, torch.float32)
+    if out.numel() < 6 * rows:
+        raise NmfHipError(f"camera_rays_at: out holds {out.numel()} values, {rows} rays need {6 * rows}")
+    m = np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise NmfHipError(f"camera_rays_at: c2w is [3, 4] or [4, 4], got {m.shape}")
+    pose = [float(v) for v in m[:3, :3].reshape(-1)] + [float(v) for v in m[:3, 3]]
+    if rows == 0:          # an empty list (its data pointer is null, which the entry point reads as "all pixels")
+        return out.view(-1)[:0].view(0, 6)
+    with torch.cuda.device(out.device):
+        _check(_lib.nmf_camera_rays_at(*pose, float(fx), float(fy), float(cx), float(cy), H, W, float(jitter[0]), float(jitter[1]),
+                                       int(seed) & 0xFFFFFFFF, _p(pix), n, ptr, _stream()), "nmf_camera_rays_at")
+    return out.view(-1)[:6 * rows].view(rows, 6)
+
+
+def accum_update(state, H, W, rgb_lin, acc, rgb_map, depth=None, normal=None, pix=None):
+    """nmf_accum_update: one pass folded into the state (a zeroed uint8 / int32 / fp32 device tensor of accum_state_bytes) for the
+    pixels pix (None: all): rgb_lin [n, 3], acc [n], rgb_map [n, 3], optionally depth [n] and normal [n, 3], indexed by list entry"""
+    H, W = int(H), int(W)
+    if not state.is_cuda or state.numel() * state.element_size() < accum_state_bytes(H, W):
+        raise NmfHipError(f"accum_update: the state is a device tensor of {accum_state_bytes(H, W)} bytes")
+    pix, n = _pixel_list(pix, "accum_update", state.device)
+    rows = H * W if pix is None else n
+    for name, t, c in (("rgb_lin", rgb_lin, 3), ("acc", acc, 1), ("rgb_map", rgb_map, 3), ("depth", depth, 1), ("normal", normal, 3)):
+        if t is None and name in ("depth", "normal"):
+            continue
+        if t is None or not t.is_cuda or t.device != state.device or t.numel() != c * rows:
+            raise NmfHipError(f"accum_update: {name} is a device tensor of {c * rows} values ({rows} pixels)")
+    f = torch.float32
+    if rows == 0:          # an empty list (its data pointer is null, which the entry point reads as "all pixels")
+        return
+    with torch.cuda.device(state.device):
+        _check(_lib.nmf_accum_update(_p(state), H, W, _p(pix), n, _p(rgb_lin, f), _p(acc, f), _p(rgb_map, f), _p(depth, f),
+                                     _p(normal, f), _stream()), "nmf_accum_update")
+
+
+def accum_active(state, H, W, min_spp, max_spp, tol, out=None, n_out=None):
+    """nmf_accum_active: the ascending int32 list of the pixels with count < min_spp, or count < max_spp and a standard error above tol
+    -> (list [H W] of which the first n_out[0] entries are written, n_out int32 [1]); both on the device, the caller reads n_out"""
+    H, W = int(H), int(W)
+    if not state.is_cuda or state.numel() * state.element_size() < accum_state_bytes(H, W):
+        raise NmfHipError(f"accum_active: the state is a device tensor of {accum_state_bytes(H, W)} bytes")
+    if out is None:
+        out = torch.empty(H * W, dtype=torch.int32, device=state.device)
+    if n_out is None:
+        n_out = torch.zeros(1, dtype=torch.int32, device=state.device)
+    if out.numel() < H * W or n_out.numel() < 1 or out.device != state.device or n_out.device != state.device:
+        raise NmfHipError(f"accum_active: out holds {H * W} int32 and n_out one, on the state's device")
+    with torch.cuda.device(state.device):
+        _check(_lib.nmf_accum_active(_p(state), H, W, int(min_spp), int(max_spp), float(tol), _p(out, torch.int32),
+                                     _p(n_out, torch.int32), _stream()), "nmf_accum_active")
+    return out, n_out
+
+
+def accum_resolve(state, H, W, bg=(1.0, 1.0, 1.0), tonemap=True, noclip=False, want=("rgb_map", "acc", "depth", "normal", "se", "count")):
+    """nmf_accum_resolve: the finished maps named in `want` -> dict(rgb_map [P, 3], acc [P], depth [P], normal [P, 3], se [P],
+    count [P] as float): the tonemap and the background of nmf_ray_compose_fwd applied to the MEAN radiance, plain means otherwise"""
+    H, W = int(H), int(W)
+    if not state.is_cuda or state.numel() * state.element_size() < accum_state_bytes(H, W):
+        raise NmfHipError(f"accum_resolve: the state is a device tensor of {accum_state_bytes(H, W)} bytes")
+    names = ("rgb_map", "acc", "depth", "normal", "se", "count")
+    if not want or set(want) - set(names):
+        raise NmfHipError(f"accum_resolve: want is a non-empty choice of {names}")
+    P = H * W
+    out = {k: torch.empty((P, 3) if k in ("rgb_map", "normal") else (P,), dtype=torch.float32, device=state.device) for k in names if k in want}
+    with torch.cuda.device(state.device):
+        _check(_lib.nmf_accum_resolve(_p(state), H, W, float(bg[0]), float(bg[1]), float(bg[2]), int(bool(tonemap)), int(bool(noclip)),
+                                      *[_p(out.get(k)) for k in names], _stream()), "nmf_accum_resolve")
     return out

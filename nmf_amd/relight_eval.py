@@ -41,10 +41,11 @@ def psnr_from_sqerr(sqerr, n_px):
 
 
 @torch.no_grad()
-def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None):
+def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None, spp=1, min_spp=4, tol=None):
     """Evaluate `nerf` (its bg_module already the new lighting) on the stacked EXR test set `test_dataset`.  Writes
     {save_path}/{idx:03d}.exr (the HDR frames), adjusted/{idx:03d}.png (the scaled, tonemapped predictions, truncated to 8 bits) and
-    stats.yaml (psnr, ssim, lpips: nan, multiplier, views).
+    stats.yaml (psnr, ssim, lpips: nan, multiplier, views).  spp > 1: the radiance and acc of a view are multisample.render_frame's
+    means of up to spp passes through the data set's rays (min_spp, tol: its adaptive stop).
     -> dict(psnrs, ssims, psnr, ssim, multiplier [3], counts, views, seconds=dict(render, metrics))"""
     from . import exr, hip
     from .renderer import _png, map_to_8bit, render_images
@@ -77,7 +78,13 @@ def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for i in range(n):
-        ims = render_images(nerf, rays_all[i].reshape(-1, rays_all.shape[-1]).to(dev), focal, chunk, noise, keys=("rgb_lin", "acc_map"))
+        view = rays_all[i].reshape(-1, rays_all.shape[-1]).to(dev)
+        if int(spp) > 1:
+            from .multisample import render_frame
+            ims, _ = render_frame(nerf, view, focal, spp=spp, min_spp=min_spp, tol=tol, jitter=False, noise=noise, chunk=chunk,
+                                  keys=("rgb_lin", "acc_map"))
+        else:
+            ims = render_images(nerf, view, focal, chunk, noise, keys=("rgb_lin", "acc_map"))
         frame = hip.relight_frame(ims["rgb_lin"].reshape(H, W, 3), ims["acc_map"].reshape(H, W))
         exr.imwrite(os.path.join(save_path, f"{i:03d}.exr"), frame.cpu().numpy())
         if on_device:

@@ -47,6 +47,16 @@ environment (the --ckpt model's own, carried along with it, or the --fixed-bg / 
 (local -> world, degrees, +z up; any subset).  --near-far is then in world units, and without it every object is marched over the range
 its box limits.  Works with --views, --path, --panels, --fixed-bg, --env-rotate and --light-turntable; orbit and spiral paths circle
 the box around all objects.  The line gains `parts` and `placements`.
+
+    python -m nmf_amd.render --ckpt log/lego.th --path orbit --spp 16 --adaptive 1 --out imgs/
+
+--spp N (nmf_amd/multisample.py) renders every frame as the mean of up to N passes per pixel, averaged in linear radiance
+on the device and tonemapped afterwards; a frame of one pass carries the Monte-Carlo grain of its secondary rays, which flickers
+along a path.  --adaptive [TOL] stops a pixel once the standard error of its displayed colour is below TOL / 255 (in 8-bit levels; without
+a value: multisample.ADAPTIVE_DEFAULT), after at least --min-spp passes (default 4).  --path frames are jittered inside the pixel; the
+views of --views, --eval-dir, --relight-eval and --light-turntable keep their rays through the pixel centres.  --path and --eval-dir
+also write spp/ (sample count) and noise/ (standard error) PNGs.  Works with --insert and --edit; --material-maps is refused (the
+material maps are not accumulated).  The line gains `sampling`.
 """
 import argparse
 import json
@@ -59,6 +69,7 @@ import torch
 from . import edit, synthetic
 from .modules.integral_equirect import IntegralEquirect
 from .modules.tensor_nerf import TensorNeRF
+from .multisample import ADAPTIVE_DEFAULT
 from .noise import DeviceNoise
 from .renderer import psnr_8bit, render_images
 
@@ -84,19 +95,24 @@ def load_fixed_bg(path, device, bg_res=512):
 
 
 @torch.no_grad()
-def render_frames(nerf, rays, focal, chunk, noise):
-    """rays [F, h*w, 6] -> rgb [F, h*w, 3], seconds; render2completion over `chunk`-ray slices (renderer.py:56-106)"""
+def render_frames(nerf, rays, focal, chunk, noise, sampling=None):
+    """rays [F, h*w, 6] -> rgb [F, h*w, 3], seconds; render2completion over `chunk`-ray slices (renderer.py:56-106).  sampling =
+    dict(spp, min_spp, tol) with spp > 1: every frame is multisample.render_frame's mean over passes of the same rays"""
     out = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for f in range(rays.shape[0]):
-        out.append(render_images(nerf, rays[f], focal, chunk, noise))
+        if sampling and sampling["spp"] > 1:
+            from .multisample import render_frame
+            out.append(render_frame(nerf, rays[f], focal, jitter=False, noise=noise, chunk=chunk, **sampling)[0]["rgb_map"])
+        else:
+            out.append(render_images(nerf, rays[f], focal, chunk, noise))
     torch.cuda.synchronize()
     return torch.stack(out), time.perf_counter() - t0
 
 
 @torch.no_grad()
-def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None):
+def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None, sampling=None):
     """view rays [1, h*w, 6] rendered n times under nerf's lighting turned by a yaw of 360 k / n: ONE map module is rewritten per frame
     (relight.rotate_env(out=)), its tables rebuild in place.  -> the keys the JSON line gains; light_%03d.png in out_dir"""
     from . import relight
@@ -112,7 +128,7 @@ def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None):
             turned.get_spherical_harmonics(100)                             # SH irradiance of the turned map
             torch.cuda.synchronize()
             env_s.append(round(time.perf_counter() - t0, 6))
-            rgb, dt = render_frames(nerf, rays, focal, chunk, noise)
+            rgb, dt = render_frames(nerf, rays, focal, chunk, noise, sampling)
             render_s.append(round(dt, 6))
             if out_dir:
                 from PIL import Image
@@ -127,7 +143,7 @@ def _model_aabb(nerf):
     return hip.host(nerf.rf.aabb).astype(np.float64).reshape(2, 3)
 
 
-def render_path(nerf, args, ds, near_far, panels, noise, dev):
+def render_path(nerf, args, ds, near_far, panels, noise, dev, sampling=None):
     """--path: the poses (nmf_amd/camera_path.py) and the camera, rendered by renderer.evaluation_path into <out>/path/ under the
     lighting the command set up (--fixed-bg, --env-rotate, --bg-res).  Without a data set the camera is --res square with the
     synthetic scene's camera_angle_x and the orbit has radius 4 at elevation 30 degrees around the origin.  -> the `path` key"""
@@ -161,9 +177,12 @@ def render_path(nerf, args, ds, near_far, panels, noise, dev):
             camera["near_far"] = list(near_far)
     out = os.path.join(args.out, "path")
     res = evaluation_path(None, nerf, c2ws, None, out, device=dev, noise=noise, panels=panels, animation=args.animation, fps=args.fps,
-                          camera=camera)
-    return dict(kind=args.path, dir=out, frames=res["frames"], panels=res["panels"], width=camera["w"], height=camera["h"],
-                seconds={k: round(v, 4) for k, v in res["seconds"].items()}, rays_per_s=round(res["rays_per_s"], 1))
+                          camera=camera, **(sampling or {}))
+    rec = dict(kind=args.path, dir=out, frames=res["frames"], panels=res["panels"], width=camera["w"], height=camera["h"],
+               seconds={k: round(v, 4) for k, v in res["seconds"].items()}, rays_per_s=round(res["rays_per_s"], 1))
+    if "rays_rendered" in res:
+        rec.update(rays_rendered=res["rays_rendered"], passes=res["passes"])
+    return rec
 
 
 def main(argv=None):
@@ -202,8 +221,28 @@ def main(argv=None):
                     help="a further trained object in the scene, repeatable: a checkpoint and its placement "
                          "'t=x,y,z;r=yaw,pitch,roll;s=scale' (local -> world, degrees, +z up; any subset; default: the identity)")
     ap.add_argument("--place", default=None, metavar="SPEC", help="the placement of the --ckpt model itself in a composed scene")
+    ap.add_argument("--spp", type=int, default=1, metavar="N",
+                    help="passes per pixel of every frame, averaged in linear radiance on the device (default 1: the single pass)")
+    ap.add_argument("--adaptive", type=float, nargs="?", const=ADAPTIVE_DEFAULT, default=None, metavar="TOL",
+                    help="with --spp: stop a pixel once the standard error of its displayed colour is below TOL / 255 "
+                         f"(8-bit levels; without a value: {ADAPTIVE_DEFAULT:g})")
+    ap.add_argument("--min-spp", type=int, default=None, metavar="N", help="with --adaptive: passes every pixel gets (default 4, at most --spp)")
     edit.add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.spp < 1:
+        ap.error("--spp is at least 1")
+    if args.adaptive is not None and args.spp < 2:
+        ap.error("--adaptive needs --spp N with N > 1 (the most passes a pixel may get)")
+    if args.adaptive is not None and not args.adaptive >= 0:
+        ap.error("--adaptive takes a tolerance of 0 or more (in 8-bit levels)")
+    if args.min_spp is not None and (args.min_spp < 1 or args.min_spp > args.spp):
+        ap.error("--min-spp lies between 1 and --spp")
+    if args.material_maps and args.spp > 1:
+        ap.error("--material-maps with --spp above 1: the material maps are not accumulated")
+    sampling = None
+    if args.spp > 1:
+        sampling = dict(spp=args.spp, min_spp=args.min_spp if args.min_spp is not None else min(4, args.spp),
+                        tol=None if args.adaptive is None else args.adaptive / 255.0)
     composed = bool(args.insert) or args.place is not None
     placements = None
     if composed:
@@ -282,11 +321,13 @@ def main(argv=None):
     chunk = args.chunk or nerf.eval_batch_size
     noise = DeviceNoise(dev, seed=11)
     render_frames(nerf, rays[:1, : min(chunk, rays.shape[1])], focal, chunk, noise)          # warm-up (table builds)
-    rgb, dt = render_frames(nerf, rays, focal, chunk, noise)
+    rgb, dt = render_frames(nerf, rays, focal, chunk, noise, sampling)
     rec = dict(frames=int(rays.shape[0]), width=wh[0], height=wh[1], chunk=chunk, seconds=round(dt, 4),
                rays_per_s=round(rays.shape[0] * rays.shape[1] / dt, 1), relit=bool(args.fixed_bg))
     if composed:
         rec.update(parts=len(placements), placements=[p.spec() for p in placements])
+    if sampling:
+        rec["sampling"] = dict(spp=sampling["spp"], min_spp=sampling["min_spp"], adaptive=args.adaptive)
     if gt is not None:
         rec["psnr"] = round(float(torch.stack([psnr_8bit(rgb[i], gt[i]) for i in range(rgb.shape[0])]).mean()), 3)
     if args.out:
@@ -296,23 +337,23 @@ def main(argv=None):
             a = (rgb[i].clip(0, 1).reshape(wh[1], wh[0], 3) * 255).byte().cpu().numpy()
             Image.fromarray(a).save(os.path.join(args.out, f"{i:03d}.png"))
     if args.light_turntable:
-        rec.update(light_turntable(nerf, rays[:1], focal, chunk, noise, args.light_turntable, wh, args.out))
+        rec.update(light_turntable(nerf, rays[:1], focal, chunk, noise, args.light_turntable, wh, args.out, sampling))
     if args.eval_dir:
         from .renderer import evaluation
         from .train import test_all_record
         t0 = time.perf_counter()
         res = evaluation(ds, nerf, None, None, args.eval_dir, N_vis=-1, device=dev, noise=noise,
-                         **(dict(material_maps=True) if args.material_maps else {}))
+                         **(dict(material_maps=True) if args.material_maps else {}), **(sampling or {}))
         rec_all = test_all_record(res)
         rec.update(ssim=rec_all["ssim"], norm_err=rec_all["norm_err"],
                    eval_seconds=dict(total=round(time.perf_counter() - t0, 4), render=round(res["seconds"]["render"], 4),
                                      metrics=round(res["seconds"]["metrics"], 4)))
     if args.relight_eval:
         from .relight_eval import relight_evaluation
-        res = relight_evaluation(nerf, ds, args.relight_eval, noise=noise, chunk=chunk)
+        res = relight_evaluation(nerf, ds, args.relight_eval, noise=noise, chunk=chunk, **(sampling or {}))
         rec["relight"] = dict(psnr=round(res["psnr"], 3), ssim=round(res["ssim"], 5), multiplier=res["multiplier"], views=res["views"])
     if args.path:
-        rec["path"] = render_path(nerf, args, ds if args.datadir else None, near_far, path_panels, noise, dev)
+        rec["path"] = render_path(nerf, args, ds if args.datadir else None, near_far, path_panels, noise, dev, sampling)
     print(json.dumps(rec), flush=True)
     return rec
 

@@ -138,6 +138,18 @@ def map_to_8bit(x):
 MATERIAL_DIRS = ("albedo", "roughness", "tint", "diffuse", "spec", "rgbd")
 
 
+SAMPLE_DIRS = ("spp", "noise")
+
+
+def write_sample_maps(savePath, name, ims, H, W):
+    """the two pictures a multi-sample frame adds (multisample.render_frame's count and se): spp/ the sample count over the frame's
+    largest, grey; noise/ the standard error of the displayed colour with 8 / 255 (eight 8-bit levels) as white, both through map_to_8bit"""
+    count, se = ims["count"].reshape(H, W), ims["se"].reshape(H, W)
+    grey = lambda t: np.repeat(map_to_8bit(t.cpu().numpy())[..., None], 3, -1)      # noqa: E731
+    _png(os.path.join(savePath, "spp", name + ".png"), grey(count / count.max().clamp(min=1.0)))
+    _png(os.path.join(savePath, "noise", name + ".png"), grey(se * (255.0 / 8.0)))
+
+
 def write_material_maps(savePath, name, ims, H, W):
     """renderer.py:433-463 for the material maps: albedo/, roughness/, tint/, diffuse/ 8-bit PNGs (map_to_8bit), spec/ and rgbd/
     (depth) float EXRs (nmf_amd/exr.py)"""
@@ -150,7 +162,7 @@ def write_material_maps(savePath, name, ims, H, W):
 
 @torch.no_grad()
 def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", N_samples=-1, white_bg=False, ndc_ray=False,
-             compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, **kw):
+             compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, spp=1, min_spp=4, tol=None, **kw):
     """renderer.py:195-510 for the outputs the fused eval pass produces.  Per view of `iterator()` ((idx, im_idx, rays,
     gt_rgb [H,W,3] or None)): PSNR of the 8-bit prediction (psnr_8bit), with compute_extra_metrics its SSIM against the
     unclipped ground truth (renderer.py:403-404, nmf_ssim), and the normal error (renderer.py:357-390, nmf_normal_err) when
@@ -161,14 +173,22 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
     sample budget are used).  material_maps: each view also renders depth and the material maps (render_images' MATERIAL_KEYS)
     and writes albedo/, roughness/, tint/, diffuse/ PNGs (map_to_8bit: the reference's truncation, clipped to [0, 1] first where
     its astype(uint8) would wrap), spec/ and rgbd/ (depth) EXRs, renderer.py:433-463.
+    spp > 1: every view is multisample.render_frame's mean of up to spp passes (min_spp, tol: its adaptive stop; the rays stay the data
+    set's, through the pixel centres, which the scores are defined on) and spp/, noise/ PNGs are written (write_sample_maps); spp = 1 is
+    the single pass as before.  The material maps are not accumulated.
     -> dict(psnrs, norm_errs, ssims, seconds=dict(render, metrics))."""
     from . import hip
     if ndc_ray:
         raise NotImplementedError("evaluation: ndc rays are not used by model=microfacet_tensorf2")
     W, H = test_dataset.img_wh
     focal = float(test_dataset.fx)
+    spp = int(spp)
+    if spp < 1:
+        raise ValueError(f"evaluate: spp is at least 1, got {spp}")
+    if spp > 1 and material_maps:
+        raise ValueError("evaluate: the material maps are not accumulated (material_maps needs spp = 1)")
     if savePath is not None:
-        for sub in ("", "world_normal", "acc_map", "err") + (MATERIAL_DIRS if material_maps else ()):
+        for sub in ("", "world_normal", "acc_map", "err") + (MATERIAL_DIRS if material_maps else ()) + (SAMPLE_DIRS if spp > 1 else ()):
             os.makedirs(os.path.join(savePath, sub), exist_ok=True)
     has_normal = getattr(test_dataset, "has_normal", None)
     acc_maps = getattr(test_dataset, "acc_maps", [])
@@ -180,7 +200,11 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         keys = ("rgb_map", "acc_map", "world_normal") + (("depth",) + MATERIAL_KEYS if material_maps else ())
-        ims = render_images(tensorf, rays.to(device), focal, noise=noise, keys=keys)
+        if spp > 1:
+            from .multisample import render_frame
+            ims, _ = render_frame(tensorf, rays.to(device), focal, spp=spp, min_spp=min_spp, tol=tol, jitter=False, noise=noise, keys=keys)
+        else:
+            ims = render_images(tensorf, rays.to(device), focal, noise=noise, keys=keys)
         rgb = ims["rgb_map"].reshape(H, W, 3)
         acc = ims["acc_map"].reshape(H, W)
         wn = ims["world_normal"].reshape(H, W, 3)
@@ -212,6 +236,8 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
                 _png(os.path.join(savePath, "err", f"{prtx}{idx:03d}.png"), (err.clamp(0, 1).cpu().numpy() * 255).astype("uint8"))
             if material_maps:
                 write_material_maps(savePath, f"{prtx}{idx:03d}", ims, H, W)
+            if spp > 1:
+                write_sample_maps(savePath, f"{prtx}{idx:03d}", ims, H, W)
     tensorf.train(was_training)
 
     final_stats = {}
@@ -235,9 +261,10 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
 
 @torch.no_grad()
 def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=5, prtx="", N_samples=-1, white_bg=False,
-               ndc_ray=False, compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, **kw):
+               ndc_ray=False, compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, spp=1, min_spp=4, tol=None,
+               **kw):
     """renderer.py:513-560: every max(N // N_vis, 1)-th view of a stacked test set (all views with N_vis < 0) through
-    `evaluate`; the call shape of train.py:863-875."""
+    `evaluate`; the call shape of train.py:863-875.  spp, min_spp, tol: evaluate's multi-sample views."""
     n = test_dataset.all_rays.shape[0]
     step = 1 if N_vis < 0 else max(n // N_vis, 1)
     idxs = list(range(0, n, step))
@@ -250,7 +277,7 @@ def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=
 
     return evaluate(iterator, test_dataset, tensorf, renderer, savePath, prtx=prtx, N_samples=N_samples, white_bg=white_bg,
                     ndc_ray=ndc_ray, compute_extra_metrics=compute_extra_metrics, device=device, noise=noise,
-                    material_maps=material_maps, **kw)
+                    material_maps=material_maps, spp=spp, min_spp=min_spp, tol=tol, **kw)
 
 
 PATH_PANELS = dict(rgb="rgb_map", depth="depth", normal="world_normal", acc="acc_map")       # panel -> key of render_images, in strip order
@@ -271,7 +298,7 @@ def _write_animation(path, frames, animation, fps):
 
 @torch.no_grad()
 def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="", device="cuda", noise=None, panels=("rgb", "depth"),
-                    animation="apng", fps=30, camera=None, writer_depth=2):
+                    animation="apng", fps=30, camera=None, writer_depth=2, spp=1, min_spp=4, tol=None):
     """renderer.py:564-582 (the call shape of train.py:884-901): renders the camera path c2ws [n, 4, 4] (camera-to-world, the loader's
     convention; nmf_amd/camera_path.py) into savePath.  `renderer` is ignored, as in `evaluation`.  The camera is test_dataset's
     (size, fx / fy, centred principal point, near_far) or camera = dict(w, h, fx, fy, cx, cy, near_far), with which test_dataset may
@@ -285,6 +312,9 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
     in flight (0: written on the calling thread); frames come out in order; an exception in the writer is raised here; the thread
     is joined before the function returns.  At the end {prtx}video.png (and {prtx}depthvideo.png with a depth panel) hold the frames
     as an animated PNG (animation="gif": .gif; "none": neither) and transforms_path.json the path (camera_path.save_path).
+    spp > 1: a frame is multisample.render_frame's mean of up to spp jittered passes from the pose (min_spp, tol: its adaptive stop;
+    one FrameAccumulator for the path; the frame's device time is all under `render`), spp/ and noise/ PNGs are written on the calling
+    thread (write_sample_maps) and the result gains rays_rendered and passes per frame.  spp = 1 runs the single pass as before.
     -> dict(frames, panels, seconds=dict(rays, render, finish: device time from events; write_wait: the calling thread blocked on
     the writer; total: wall clock until the last frame is on disk; animation: the container), frame_ms=dict(rays, render, finish:
     the device times per frame), rays_per_s)."""
@@ -304,9 +334,16 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    for sub in ("",) + tuple(PATH_DIRS[p] for p in panels if p in PATH_DIRS):
+    spp = int(spp)
+    if spp < 1:
+        raise ValueError(f"evaluation_path: spp is at least 1, got {spp}")
+    for sub in ("",) + tuple(PATH_DIRS[p] for p in panels if p in PATH_DIRS) + (SAMPLE_DIRS if spp > 1 else ()):
         os.makedirs(os.path.join(savePath, sub), exist_ok=True)
     keys = tuple(PATH_PANELS[p] for p in panels)
+    accumulator, sampled = None, []
+    if spp > 1:
+        from .multisample import FrameAccumulator, render_frame
+        accumulator = FrameAccumulator(H, W, device)
     rays = torch.empty((H * W, 6), dtype=torch.float32, device=device)
     strip = torch.empty((H, len(panels) * W, 3), dtype=torch.uint8, device=device)
     pool = queue.Queue()
@@ -353,10 +390,17 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
         for k in range(n):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]      # rays 0-1, render 1-2, finish 3-4
             ev[0].record()
-            hip.camera_rays(c2ws[k], cam["fx"], cam["fy"], cam["cx"], cam["cy"], H, W, out=rays)
-            ev[1].record()
-            ims = render_images(tensorf, rays, float(cam["fx"]), noise=noise, keys=keys)
-            ims = dict(rgb_map=ims) if keys == ("rgb_map",) else ims
+            if spp > 1:
+                ev[1].record()
+                ims, st = render_frame(tensorf, c2ws[k], cam, spp=spp, min_spp=min_spp, tol=tol, jitter=True, noise=noise, keys=keys,
+                                       accumulator=accumulator)
+                sampled.append(st)
+                write_sample_maps(savePath, f"{prtx}{k:03d}", ims, H, W)
+            else:
+                hip.camera_rays(c2ws[k], cam["fx"], cam["fy"], cam["cx"], cam["cy"], H, W, out=rays)
+                ev[1].record()
+                ims = render_images(tensorf, rays, float(cam["fx"]), noise=noise, keys=keys)
+                ims = dict(rgb_map=ims) if keys == ("rgb_map",) else ims
             ev[2].record()
             tw = time.perf_counter()
             pin = pool.get()                          # a free pinned buffer: blocks while writer_depth frames are in flight
@@ -401,7 +445,10 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
     angle = 2.0 * float(np.arctan(0.5 * W / cam["fx"]))
     camera_path.save_path(os.path.join(savePath, "transforms_path.json"), c2ws, angle, W, H, near_far,
                           intrinsics=(cam["fx"], cam["fy"], cam["cx"], cam["cy"]))
-    return dict(frames=n, panels=list(panels),
-                seconds=dict(rays=dev_s[0], render=dev_s[1], finish=dev_s[2], write_wait=t_wait, total=total,
-                             animation=time.perf_counter() - t1),
-                frame_ms=frame_ms, rays_per_s=n * H * W / total if total > 0 else 0.0)
+    res = dict(frames=n, panels=list(panels),
+               seconds=dict(rays=dev_s[0], render=dev_s[1], finish=dev_s[2], write_wait=t_wait, total=total,
+                            animation=time.perf_counter() - t1),
+               frame_ms=frame_ms, rays_per_s=n * H * W / total if total > 0 else 0.0)
+    if spp > 1:
+        res.update(rays_rendered=[st["rays_rendered"] for st in sampled], passes=[st["passes"] for st in sampled])
+    return res
