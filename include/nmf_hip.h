@@ -978,6 +978,64 @@ int nmf_accum_active(void* state, int32_t H, int32_t W, int32_t min_spp, int32_t
 int nmf_accum_resolve(const void* state, int32_t H, int32_t W, float bg_r, float bg_g, float bg_b, int32_t tonemap, int32_t noclip,
                       float* rgb_map, float* acc, float* depth, float* normal, float* se, float* count, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Denoised frames: a variance-guided, edge-stopping a-trous wavelet filter over the finished state of a multi-sample frame
+ * (nmf_amd/multisample.py:FrameAccumulator.denoise, csrc/denoise.hip; spatial only -- SVGF without its temporal
+ * part; the reference has no counterpart).  Not on the training path.  Added without a bump of NMF_ABI_VERSION: nothing existing
+ * changed.
+ *
+ * Every quantity is fp32 with one rounding per operation, and the only operations are + - * / max fabs (sqrt once, for se), so the
+ * kernels are restated bit for bit in numpy fp32.  One lane per pixel, plain loads and stores, no atomics: two runs give the same
+ * bytes.  Pixel p = y W + x.  Read per pixel from the state of nmf_accum_* (its planes, above):
+ *     L = mean rgb_lin [3] | A = mean acc | C = mean rgb_map [3], the guide colour in display units | Z = mean depth |
+ *     N = mean normal [3], as stored | V = max_c (M2_c / ((float)n (float)(n - 1))) for a count n >= 2, else 0        (V = se^2)
+ *
+ * Workspace.  nmf_denoise_workspace_bytes(H, W) bytes (0 for a frame that would be refused), 4-byte aligned, need not be zeroed:
+ * NMF_DENOISE_PLANES planes of P words, plane k of pixel p at word k P + p --
+ *     0 fixed (int32) | 1 gx | 2 gy | 3-10 set 0: L [3], A, C [3], Vg | 11-18 set 1 likewise
+ * N and Z are never filtered and are read from the state by every level.
+ *
+ * nmf_denoise_prepare (one launch): fixed = (V == 0); with indices clamped to the frame,
+ *     r_j = (V[y+j][x-1] + 2 V[y+j][x]) + V[y+j][x+1]  for j = -1, 0, 1;   Vg = ((r_-1 + 2 r_0) + r_1) * 0.0625
+ *     gx = (Z[y][x+1] - Z[y][x-1]) * 0.5;   gy = (Z[y+1][x] - Z[y-1][x]) * 0.5
+ *   and L, A, C copied into set 0.
+ *
+ * nmf_denoise_level (one launch): reads set `src`, writes set 1 - src, with step s.  A fixed pixel copies its eight values bit for
+ *   bit.  Otherwise the taps (i, j) run over {-2..2}^2, i outermost, q = (y + s i, x + s j); a tap outside the frame is skipped (both
+ *   coordinates are checked before anything is read).  h = b_i b_j with b = (1, 4, 6, 4, 1) / 16 (exact).  The centre has w = h.
+ *   Every other tap, with kc2 = k_c k_c, kn2 = k_n k_n, ka2 = k_a k_a (fp32 products taken on the host):
+ *     d = ((dC_0^2 + dC_1^2) + dC_2^2) / (kc2 (Vg_p + Vg_q) + 1e-10)                      dC = C_p - C_q
+ *     d = d + ((dN_0^2 + dN_1^2) + dN_2^2) / kn2                                          dN = N_p - N_q
+ *     e = k_z fabs(gx_p (float)(s j) + gy_p (float)(s i)) + eps_z;   d = d + ((Z_p - Z_q) (Z_p - Z_q)) / (e e)
+ *     d = d + ((A_p - A_q) (A_p - A_q)) / ka2
+ *     t = max(0, 1 - d)  (0 for a NaN);   a tap with t = 0 is skipped;   w = (h t) t
+ *   and in tap order  sw += w;  sL_c += w L_q;  sC_c += w C_q;  sA += w A_q;  sV += (w w) Vg_q.  Then
+ *     L' = sL / sw,  C' = sC / sw,  A' = sA / sw,  Vg' = sV / (sw sw)                     (sw >= 36 / 256: the centre)
+ *   A pixel to which no tap beside the centre contributed copies its eight values like a fixed one ((h x) / h need not return x).
+ *   The kernel has compact support: nothing crosses an edge of depth, normal or coverage with d >= 1.  Vg' steers the colour test
+ *   of the next level; it is a guide, not an estimate of the remaining error (the levels' inputs are correlated).
+ *
+ * nmf_denoise_finish (one launch) from set `src`, each output may be NULL: rgb_map [P][3] = (tonemap ? srgb(L) : L) + (1 - A) bg,
+ *   the device function and flags of nmf_accum_resolve; rgb_lin [P][3] = L; acc [P] = A; se [P] = sqrt(Vg).  Straight after
+ *   nmf_denoise_prepare (src = 0) rgb_map, rgb_lin and acc are nmf_accum_resolve's bytes.
+ *
+ * nmf_denoise: prepare, level l = 0 .. levels - 1 with s = 2^l and src = l & 1, finish with src = levels & 1, on the stream.
+ *
+ * Refused with nothing launched (NMF_EINVAL): H or W below 1; levels outside [0, NMF_DENOISE_MAX_LEVELS]; step outside
+ * [1, 2^NMF_DENOISE_MAX_LEVELS]; src not 0 or 1; a k_* or eps_z that is not finite and positive; a bg that is not finite; a NULL or
+ * misaligned state or workspace; all outputs NULL.  H W above 2^31 - 1: NMF_ERANGE. */
+#define NMF_DENOISE_PLANES 19
+#define NMF_DENOISE_MAX_LEVELS 8
+int64_t nmf_denoise_workspace_bytes(int32_t H, int32_t W);
+int nmf_denoise_prepare(const void* state, void* workspace, int32_t H, int32_t W, void* stream);
+int nmf_denoise_level(const void* state, void* workspace, int32_t H, int32_t W, int32_t step, int32_t src, float k_c, float k_n,
+                      float k_z, float eps_z, float k_a, void* stream);
+int nmf_denoise_finish(const void* workspace, int32_t H, int32_t W, int32_t src, float bg_r, float bg_g, float bg_b, int32_t tonemap,
+                       int32_t noclip, float* rgb_map, float* rgb_lin, float* acc, float* se, void* stream);
+int nmf_denoise(const void* state, void* workspace, int32_t H, int32_t W, int32_t levels, float k_c, float k_n, float k_z, float eps_z,
+                float k_a, float bg_r, float bg_g, float bg_b, int32_t tonemap, int32_t noclip, float* rgb_map, float* rgb_lin,
+                float* acc, float* se, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,22 +10,16 @@
 // and sqrtf are hipcc's correctly rounded fp32 forms (as in camera.hip), and the one power of the tonemap is taken in double and
 // rounded to fp32 once, which is the correctly rounded fp32 power wherever the double result is not within an ulp (of double) of
 // a rounding boundary -- numpy's route is the same.
-#include "common.hpp"
-
-#include <math.h>
+#include "accum_planes.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using namespace accum;      // the planes of the state, finite_f, check_frame, srgb / displayed (shared with denoise.hip)
+
 constexpr int ACC_BLOCK = 256;                 // lanes of a workgroup = pixels of a scan tile (NMF_ACCUM_TILE)
 static_assert(ACC_BLOCK == NMF_ACCUM_TILE, "the tile of the list is one workgroup");
-
-// planes of the state, P 4-byte words each (NMF_ACCUM_PLANES of them), then one int32 per tile
-enum { PL_COUNT = 0, PL_LIN = 1, PL_ACC = 4, PL_DEPTH = 5, PL_NORMAL = 6, PL_MAP = 9, PL_M2 = 12, PL_END = 15 };
-static_assert(PL_END == NMF_ACCUM_PLANES, "state planes");
-
-inline bool finite_f(float v) { return fabsf(v) <= 3.4028235e38f; }      // (false for a NaN)
 
 __device__ __forceinline__ float nan0(float v) { return v != v ? 0.f : v; }
 
@@ -213,14 +207,6 @@ __global__ void __launch_bounds__(ACC_BLOCK) k_active_emit(const float* __restri
 }
 
 // ---- the finished maps -------------------------------------------------------------------------------------------------------------
-constexpr float SRGB_LIMIT = 0.0031308f;
-
-__device__ __forceinline__ float srgb(float x, int noclip) {
-    // nmf_ray_compose_fwd's formula (modules/tonemap.py:34-55); the power in double, rounded once
-    const float o = x > SRGB_LIMIT ? 1.055f * (float)pow((double)fmaxf(x, SRGB_LIMIT), 1.0 / 2.4) - 0.055f : 12.92f * x;
-    return noclip ? o : fminf(fmaxf(o, 0.f), 1.f);
-}
-
 struct ResolveArgs {
     const float* state;
     int64_t P;
@@ -239,7 +225,7 @@ __global__ void __launch_bounds__(ACC_BLOCK) k_accum_resolve(ResolveArgs A) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float v = A.state[(int64_t)(PL_LIN + k) * A.P + p];
-            A.rgb_map[p * 3 + k] = (A.tonemap ? srgb(v, A.noclip) : v) + t * A.bg[k];
+            A.rgb_map[p * 3 + k] = displayed(v, t, A.bg[k], A.tonemap, A.noclip);
         }
     }
     if (A.acc) A.acc[p] = a;
@@ -250,12 +236,6 @@ __global__ void __launch_bounds__(ACC_BLOCK) k_accum_resolve(ResolveArgs A) {
     }
     if (A.se) A.se[p] = std_err(A.state, A.P, p, count);
     if (A.count) A.count[p] = (float)count;
-}
-
-int check_frame(int32_t H, int32_t W, const char* below, const char* above) {
-    NMF_REQUIRE(H >= 1 && W >= 1, NMF_EINVAL, below);
-    NMF_REQUIRE((int64_t)H * W <= 2147483647LL, NMF_ERANGE, above);
-    return NMF_OK;
 }
 
 }  // namespace

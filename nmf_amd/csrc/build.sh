@@ -15,7 +15,7 @@ for f in "$here"/*.hip; do
     extra=""
     # bookkeeping kernels must reproduce the CPU oracle bit-for-bit: no a*b+c -> fma contraction there
     case "$(basename "$f")" in
-      march.hip|select.hip|composite.hip|env.hip|metrics.hip|mesh.hip|tv.hip|relight_eval.hip|camera.hip|edit.hip|atlas.hip|compose.hip|accum.hip) extra="-ffp-contract=off" ;;
+      march.hip|select.hip|composite.hip|env.hip|metrics.hip|mesh.hip|tv.hip|relight_eval.hip|camera.hip|edit.hip|atlas.hip|compose.hip|accum.hip|denoise.hip) extra="-ffp-contract=off" ;;
       # the MLP backward keeps 128 accumulator registers alive across its loop: transient MFMA results go to VGPRs directly
       # (the default picks the AGPR form for every MFMA of a 512-register kernel and copies each result out)
       brdf_mlp.hip) extra="-mllvm -amdgpu-mfma-vgpr-form=1" ;;

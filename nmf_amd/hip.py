@@ -104,6 +104,7 @@ EXPORTS = [
     "nmf_atlas_texels", "nmf_atlas_store",
     "nmf_rays_place", "nmf_merge_rank", "nmf_merge_scatter",
     "nmf_accum_state_bytes", "nmf_camera_rays_at", "nmf_accum_update", "nmf_accum_active", "nmf_accum_resolve",
+    "nmf_denoise_workspace_bytes", "nmf_denoise_prepare", "nmf_denoise_level", "nmf_denoise_finish", "nmf_denoise",
 ]
 for _n in EXPORTS:
     if not hasattr(_lib, _n):
@@ -1402,3 +1403,89 @@ def accum_resolve(state, H, W, bg=(1.0, 1.0, 1.0), tonemap=True, noclip=False, w
         _check(_lib.nmf_accum_resolve(_p(state), H, W, float(bg[0]), float(bg[1]), float(bg[2]), int(bool(tonemap)), int(bool(noclip)),
                                       *[_p(out.get(k)) for k in names], _stream()), "nmf_accum_resolve")
     return out
+
+
+# ---- denoised frames: the variance-guided a-trous filter over the accumulator state (csrc/denoise.hip; nmf_amd/multisample.py) ---------
+DENOISE_PLANES, DENOISE_MAX_LEVELS = 19, 8          # NMF_DENOISE_PLANES, NMF_DENOISE_MAX_LEVELS of include/nmf_hip.h
+DENOISE_OUTPUTS = ("rgb_map", "rgb_lin", "acc", "se")
+
+
+def denoise_workspace_bytes(H, W):
+    """nmf_denoise_workspace_bytes: the bytes of the filter's workspace for an H x W frame (host arithmetic)"""
+    n = int(_lib.nmf_denoise_workspace_bytes(int(H), int(W)))
+    if n <= 0:
+        raise NmfHipError(f"denoise_workspace_bytes: a frame is at least 1 x 1 and at most 2^31 - 1 pixels, got {H} x {W}")
+    return n
+
+
+def _denoise_buffers(what, H, W, state, workspace):
+    for name, t, need in (("state", state, accum_state_bytes), ("workspace", workspace, denoise_workspace_bytes)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.numel() * t.element_size() < need(H, W):
+            raise NmfHipError(f"{what}: the {name} is a device tensor of {need(H, W)} bytes")
+    if state is not None and workspace is not None and state.device != workspace.device:
+        raise NmfHipError(f"{what}: the state and the workspace are on one device")
+
+
+def _denoise_outputs(what, P, want, out, device):
+    if not want or set(want) - set(DENOISE_OUTPUTS):
+        raise NmfHipError(f"{what}: want is a non-empty choice of {DENOISE_OUTPUTS}")
+    res = {}
+    for k in DENOISE_OUTPUTS:
+        if k not in want:
+            continue
+        n = 3 * P if k in ("rgb_map", "rgb_lin") else P
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty((P, 3) if n == 3 * P else (P,), dtype=torch.float32, device=device)
+        elif not t.is_cuda or t.device != device or t.dtype != torch.float32 or t.numel() != n:
+            raise NmfHipError(f"{what}: out['{k}'] is a float32 tensor of {n} values on the workspace's device")
+        res[k] = t
+    return res
+
+
+def denoise_prepare(state, workspace, H, W):
+    """nmf_denoise_prepare: fixed, the blurred variance, the depth gradient and set 0 of the workspace from the accumulator state"""
+    H, W = int(H), int(W)
+    _denoise_buffers("denoise_prepare", H, W, state, workspace)
+    with torch.cuda.device(state.device):
+        _check(_lib.nmf_denoise_prepare(_p(state), _p(workspace), H, W, _stream()), "nmf_denoise_prepare")
+
+
+def denoise_level(state, workspace, H, W, step, src, k_c, k_n, k_z, eps_z, k_a):
+    """nmf_denoise_level: one a-trous level of step `step` from set `src` (0 / 1) of the workspace into the other"""
+    H, W = int(H), int(W)
+    _denoise_buffers("denoise_level", H, W, state, workspace)
+    with torch.cuda.device(state.device):
+        _check(_lib.nmf_denoise_level(_p(state), _p(workspace), H, W, int(step), int(src), float(k_c), float(k_n), float(k_z),
+                                      float(eps_z), float(k_a), _stream()), "nmf_denoise_level")
+
+
+def denoise_finish(workspace, H, W, src, bg=(1.0, 1.0, 1.0), tonemap=True, noclip=False, want=("rgb_map",), out=None):
+    """nmf_denoise_finish: the maps named in `want` from set `src` -> dict(rgb_map [P, 3], rgb_lin [P, 3], acc [P], se [P] = sqrt(Vg));
+    out: tensors to fill instead of new ones, by name"""
+    H, W = int(H), int(W)
+    _denoise_buffers("denoise_finish", H, W, None, workspace)
+    res = _denoise_outputs("denoise_finish", H * W, want, out, workspace.device)
+    with torch.cuda.device(workspace.device):
+        _check(_lib.nmf_denoise_finish(_p(workspace), H, W, int(src), float(bg[0]), float(bg[1]), float(bg[2]), int(bool(tonemap)),
+                                       int(bool(noclip)), *[_p(res.get(k), torch.float32) for k in DENOISE_OUTPUTS], _stream()),
+               "nmf_denoise_finish")
+    return res
+
+
+def denoise(state, H, W, levels, k_c, k_n, k_z, eps_z, k_a, bg=(1.0, 1.0, 1.0), tonemap=True, noclip=False, want=("rgb_map",),
+            workspace=None, out=None):
+    """nmf_denoise: prepare, `levels` levels of steps 1, 2, 4, ... and finish on the current stream -> denoise_finish's dict.
+    workspace: a device tensor of denoise_workspace_bytes to reuse (default: a new one)"""
+    H, W = int(H), int(W)
+    if workspace is None:
+        workspace = torch.empty(denoise_workspace_bytes(H, W) // 4, dtype=torch.float32, device=state.device)
+    _denoise_buffers("denoise", H, W, state, workspace)
+    res = _denoise_outputs("denoise", H * W, want, out, workspace.device)
+    with torch.cuda.device(state.device):
+        _check(_lib.nmf_denoise(_p(state), _p(workspace), H, W, int(levels), float(k_c), float(k_n), float(k_z), float(eps_z), float(k_a),
+                                float(bg[0]), float(bg[1]), float(bg[2]), int(bool(tonemap)), int(bool(noclip)),
+                                *[_p(res.get(k), torch.float32) for k in DENOISE_OUTPUTS], _stream()), "nmf_denoise")
+    return res

@@ -5,7 +5,14 @@ LINEAR radiance, tonemaps the mean, jitters the sub-pixel position when the rays
 the pixels whose standard error in display units is still above `tol`.  The reference renders one sample per pixel.
 
 The kernels are csrc/accum.hip (include/nmf_hip.h, "Multi-sample frames"): nmf_camera_rays_at, nmf_accum_update, nmf_accum_active,
-nmf_accum_resolve.  With spp = 1 nothing here runs: renderer.evaluation_path / evaluate keep their single-pass code."""
+nmf_accum_resolve.  With spp = 1 nothing here runs: renderer.evaluation_path / evaluate keep their single-pass code.
+
+Denoised frames (csrc/denoise.hip, include/nmf_hip.h "Denoised frames"): render_frame(denoise=DenoiseParams()) runs a
+variance-guided, edge-stopping a-trous filter over the finished state -- the grain sits in the specular term, and a pixel whose samples
+all agreed (se = 0: the background, unscattered pixels) leaves with its bits.  Off by default: without `denoise` nothing new runs."""
+import dataclasses
+import math
+
 import numpy as np
 import torch
 
@@ -14,6 +21,35 @@ PLASTIC = (0.7548776662, 0.5698402910)
 FRAME_KEYS = ("rgb_map", "acc_map", "depth", "world_normal", "rgb_lin")
 # `--adaptive` without a value, in 8-bit levels (tol = ADAPTIVE_DEFAULT / 255): chosen from the table of DESIGN.md 10.11
 ADAPTIVE_DEFAULT = 1.0
+
+
+@dataclasses.dataclass(frozen=True)
+class DenoiseParams:
+    """The six numbers of the filter (include/nmf_hip.h, "Denoised frames"): levels of steps 1, 2, 4, ... (0 to 8; 0 is the undenoised
+    frame), and the widths of the four edge tests -- k_c in standard errors of the displayed colour (the strength), k_n on the
+    difference of the mean normals, k_z in depth gradients per pixel with eps_z the slack of a flat surface, k_a on the coverage.
+    The defaults are the setting of DESIGN.md 10.12's table with the lowest error at 4 spp."""
+    levels: int = 3
+    k_c: float = 4.0
+    k_n: float = 0.5
+    k_z: float = 2.0
+    eps_z: float = 0.02
+    k_a: float = 0.25
+
+    def __post_init__(self):
+        if isinstance(self.levels, bool) or int(self.levels) != self.levels or not 0 <= self.levels <= 8:
+            raise ValueError(f"DenoiseParams: levels is an integer in [0, 8], got {self.levels}")
+        for name in ("k_c", "k_n", "k_z", "eps_z", "k_a"):
+            v = float(getattr(self, name))
+            if not (math.isfinite(v) and v > 0.0):
+                raise ValueError(f"DenoiseParams: {name} is finite and positive, got {v}")
+
+    def record(self):
+        """the parameters as a JSON-able dict (the `sampling` record of nmf_amd.render)"""
+        return {k: (int(v) if k == "levels" else float(v)) for k, v in dataclasses.asdict(self).items()}
+
+
+DENOISE_KEYS = ("rgb_map", "rgb_lin", "acc_map", "se")
 
 
 def pass_offset(k):
@@ -35,6 +71,7 @@ class FrameAccumulator:
                                    world_normal, rows indexed by the entries of pix; None: all pixels)
       active(min_spp, max_spp, tol) -> (pix int32 [n] ascending, n): the pixels that still need samples; ONE read-back of n
       resolve(...)                 -> dict(rgb_map, acc_map, depth, world_normal, se, count) of the keys asked for
+      denoise(params, ...)         -> dict(rgb_map, rgb_lin, acc_map, se) of the keys asked for: the filtered frame (DenoiseParams)
       reset()                      zeroes the state for the next frame"""
 
     def __init__(self, H, W, device="cuda"):
@@ -75,6 +112,27 @@ class FrameAccumulator:
             res["rgb_lin"] = hip.accum_resolve(self.state, self.H, self.W, bg=(0.0, 0.0, 0.0), tonemap=False, want=("rgb_map",))["rgb_map"]
         return res
 
+    def denoise(self, params, bg=(1.0, 1.0, 1.0), tonemap=True, noclip=False, keys=("rgb_map",), frame_hw=None):
+        """The a-trous filter over the state as it stands (the state is only read; the workspace is kept for the next frame) ->
+        dict of the `keys` among rgb_map [P, 3], rgb_lin [P, 3], acc_map [P] (filtered) and se [P] = sqrt of the propagated variance
+        guide (not an error estimate).  frame_hw: the (H, W) the P pixels form when the accumulator was made for a ray array (1 x P)."""
+        from . import hip
+        if not isinstance(params, DenoiseParams):
+            raise TypeError("FrameAccumulator.denoise: params is a DenoiseParams")
+        H, W = (self.H, self.W) if frame_hw is None else (int(frame_hw[0]), int(frame_hw[1]))
+        if H < 1 or W < 1 or H * W != self.H * self.W:
+            raise ValueError(f"FrameAccumulator.denoise: frame_hw = {frame_hw} does not hold the accumulator's {self.H * self.W} pixels")
+        names = dict(rgb_map="rgb_map", rgb_lin="rgb_lin", acc_map="acc", se="se")
+        want = [k for k in DENOISE_KEYS if k in keys]
+        if not want or set(keys) - set(DENOISE_KEYS):
+            raise ValueError(f"FrameAccumulator.denoise: keys are a non-empty choice of {DENOISE_KEYS}")
+        ws = getattr(self, "_denoise_ws", None)
+        if ws is None:
+            ws = self._denoise_ws = torch.empty(hip.denoise_workspace_bytes(H, W) // 4, dtype=torch.float32, device=self.device)
+        out = hip.denoise(self.state, H, W, params.levels, params.k_c, params.k_n, params.k_z, params.eps_z, params.k_a, bg=bg,
+                          tonemap=tonemap, noclip=noclip, want=tuple(names[k] for k in want), workspace=ws)
+        return {k: out[names[k]] for k in want}
+
 
 def _is_pose(x):
     return tuple(getattr(x, "shape", ())) in ((3, 4), (4, 4))
@@ -82,7 +140,7 @@ def _is_pose(x):
 
 @torch.no_grad()
 def render_frame(nerf, rays_or_pose, focal_or_camera, *, spp, min_spp=4, tol=None, jitter=True, noise=None, keys=("rgb_map",),
-                 chunk=None, accumulator=None, render=None):
+                 chunk=None, accumulator=None, render=None, denoise=None, frame_hw=None):
     """One view of `nerf` (a TensorNeRF, also inside relight.relit, or a ComposedScene: what render_images takes) from up to `spp`
     passes per pixel.
 
@@ -100,14 +158,24 @@ def render_frame(nerf, rays_or_pose, focal_or_camera, *, spp, min_spp=4, tol=Non
     depth [P], world_normal [P, 3], rgb_lin [P, 3]: plain means) plus se [P] and count [P] (float); stats = dict(passes, rays_rendered).
     chunk: render_images' rays per chunk (default: the model's eval_batch_size).  accumulator / render: the FrameAccumulator to use
     (reset first; default: a new one) and the pass renderer (default: renderer.render_images) -- the seam the CPU tests drive the
-    loop through."""
+    loop through.
+
+    denoise: a DenoiseParams -- the finished state goes through FrameAccumulator.denoise, and rgb_map (and rgb_lin, when asked for)
+    are the filtered ones; every other map, se and count among them, stays the measured one, and "rgb_raw" in keys adds the
+    undenoised rgb_map.  It needs spp >= 2 (one sample has no variance).  The filter needs the frame's shape: a pose brings it, a ray
+    array needs frame_hw = (H, W) with H W = P (its accumulator stays 1 x P for the passes).  None (the default): nothing new runs."""
     spp, min_spp = int(spp), int(min_spp)
     if spp < 1 or min_spp < 1:
         raise ValueError(f"render_frame: spp and min_spp are at least 1, got {spp} and {min_spp}")
     if tol is not None and not float(tol) >= 0.0:
         raise ValueError(f"render_frame: tol is None (fixed count) or at least 0, got {tol}")
-    if set(keys) - set(FRAME_KEYS):
+    if set(keys) - set(FRAME_KEYS) - ({"rgb_raw"} if denoise is not None else set()):
         raise ValueError(f"render_frame: keys are a choice of {FRAME_KEYS}; the material maps are not accumulated")
+    if denoise is not None:
+        if not isinstance(denoise, DenoiseParams):
+            raise TypeError("render_frame: denoise is a DenoiseParams or None")
+        if spp < 2:
+            raise ValueError(f"render_frame: denoise needs spp >= 2 (the variance of one sample is unknown), got spp = {spp}")
     min_spp = min(min_spp, spp)
     if render is None:
         from .renderer import render_images as render
@@ -123,12 +191,20 @@ def render_frame(nerf, rays_or_pose, focal_or_camera, *, spp, min_spp=4, tol=Non
         rays_all = rays_or_pose
         H, W, focal = 1, int(rays_all.shape[0]), float(focal_or_camera)
         device = rays_all.device
+    if denoise is not None:
+        if pose:
+            if frame_hw is not None and (int(frame_hw[0]), int(frame_hw[1])) != (H, W):
+                raise ValueError(f"render_frame: frame_hw = {tuple(frame_hw)} is not the camera's {H} x {W}")
+            frame_hw = (H, W)
+        elif frame_hw is None or len(frame_hw) != 2 or min(int(v) for v in frame_hw) < 1 or int(frame_hw[0]) * int(frame_hw[1]) != H * W:
+            raise ValueError(f"render_frame: denoise with a ray array needs frame_hw = (H, W) with H W = {H * W} rays, got {frame_hw}")
     acc = accumulator if accumulator is not None else FrameAccumulator(H, W, device)
     if accumulator is not None:
         if acc.H * acc.W != H * W:
             raise ValueError(f"render_frame: the accumulator holds {acc.H} x {acc.W} pixels, the frame has {H * W}")
         acc.reset()
-    need = ("rgb_map", "acc_map", "rgb_lin") + tuple(k for k in ("depth", "world_normal") if k in keys)
+    # (the filter's edge guides are the depth and normal means: a denoised frame accumulates both whatever the caller asked for)
+    need = ("rgb_map", "acc_map", "rgb_lin") + tuple(k for k in ("depth", "world_normal") if k in keys or denoise is not None)
     P = H * W
     passes = rays_rendered = 0
     for k in range(spp):
@@ -147,5 +223,17 @@ def render_frame(nerf, rays_or_pose, focal_or_camera, *, spp, min_spp=4, tol=Non
         acc.update(render(nerf, rays, focal, chunk=chunk, noise=noise, keys=need), pix)
         passes += 1
         rays_rendered += n
-    ims = acc.resolve(bg=(1.0, 1.0, 1.0), tonemap=True, noclip=bool(getattr(nerf, "hdr", False)), keys=tuple(keys))
+    noclip = bool(getattr(nerf, "hdr", False))
+    if denoise is None:
+        ims = acc.resolve(bg=(1.0, 1.0, 1.0), tonemap=True, noclip=noclip, keys=tuple(keys))
+        return ims, dict(passes=passes, rays_rendered=rays_rendered)
+    # the measured maps first (rgb_lin comes from the filter; the undenoised rgb_map only where rgb_raw asks for it), then the filter
+    ims = acc.resolve(bg=(1.0, 1.0, 1.0), tonemap=True, noclip=noclip,
+                      keys=tuple(k for k in keys if k not in ("rgb_raw", "rgb_lin")) + (("rgb_map",) if "rgb_raw" in keys else ()))
+    if "rgb_raw" in keys:
+        ims["rgb_raw"] = ims["rgb_map"]
+    if "rgb_map" not in keys:
+        ims.pop("rgb_map", None)
+    den = acc.denoise(denoise, bg=(1.0, 1.0, 1.0), tonemap=True, noclip=noclip, keys=("rgb_map", "rgb_lin"), frame_hw=frame_hw)
+    ims.update({k: den[k] for k in ("rgb_map", "rgb_lin") if k in keys})
     return ims, dict(passes=passes, rays_rendered=rays_rendered)

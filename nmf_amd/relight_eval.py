@@ -41,11 +41,12 @@ def psnr_from_sqerr(sqerr, n_px):
 
 
 @torch.no_grad()
-def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None, spp=1, min_spp=4, tol=None):
+def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None, spp=1, min_spp=4, tol=None, denoise=None):
     """Evaluate `nerf` (its bg_module already the new lighting) on the stacked EXR test set `test_dataset`.  Writes
     {save_path}/{idx:03d}.exr (the HDR frames), adjusted/{idx:03d}.png (the scaled, tonemapped predictions, truncated to 8 bits) and
     stats.yaml (psnr, ssim, lpips: nan, multiplier, views).  spp > 1: the radiance and acc of a view are multisample.render_frame's
-    means of up to spp passes through the data set's rays (min_spp, tol: its adaptive stop).
+    means of up to spp passes through the data set's rays (min_spp, tol: its adaptive stop); denoise: a multisample.DenoiseParams, the
+    radiance is then the filtered one (needs spp >= 2; the coverage stays the measured mean).
     -> dict(psnrs, ssims, psnr, ssim, multiplier [3], counts, views, seconds=dict(render, metrics))"""
     from . import exr, hip
     from .renderer import _png, map_to_8bit, render_images
@@ -53,6 +54,8 @@ def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None, sp
         raise ValueError("relighting evaluation needs an EXR test set (linear ground truth with alpha)")
     W, H = test_dataset.img_wh
     focal = float(test_dataset.fx)
+    if denoise is not None and int(spp) < 2:
+        raise ValueError(f"relight_evaluation: denoise needs spp >= 2, got spp = {spp}")
     rays_all = test_dataset.all_rays
     if rays_all.dim() != 3:
         raise ValueError("relighting evaluation needs a stacked test set (is_stack=True)")
@@ -82,7 +85,7 @@ def relight_evaluation(nerf, test_dataset, save_path, noise=None, chunk=None, sp
         if int(spp) > 1:
             from .multisample import render_frame
             ims, _ = render_frame(nerf, view, focal, spp=spp, min_spp=min_spp, tol=tol, jitter=False, noise=noise, chunk=chunk,
-                                  keys=("rgb_lin", "acc_map"))
+                                  keys=("rgb_lin", "acc_map"), denoise=denoise, frame_hw=(H, W) if denoise is not None else None)
         else:
             ims = render_images(nerf, view, focal, chunk, noise, keys=("rgb_lin", "acc_map"))
         frame = hip.relight_frame(ims["rgb_lin"].reshape(H, W, 3), ims["acc_map"].reshape(H, W))

@@ -57,6 +57,14 @@ a value: multisample.ADAPTIVE_DEFAULT), after at least --min-spp passes (default
 views of --views, --eval-dir, --relight-eval and --light-turntable keep their rays through the pixel centres.  --path and --eval-dir
 also write spp/ (sample count) and noise/ (standard error) PNGs.  Works with --insert and --edit; --material-maps is refused (the
 material maps are not accumulated).  The line gains `sampling`.
+
+    python -m nmf_amd.render --ckpt log/lego.th --path orbit --spp 4 --denoise --out imgs/
+
+--denoise [LEVELS] (with --spp 2 or more; multisample.DenoiseParams) filters every finished frame with the
+variance-guided, edge-stopping a-trous filter of csrc/denoise.hip: LEVELS levels of steps 1, 2, 4, ... (default 3, at most 8), stopped
+by the frame's own mean depth, normal and coverage; pixels whose samples all agreed keep their bytes.  --denoise-strength K_C is the
+width of the colour test in standard errors (default 4; larger smooths more).  Works with everything --spp works with, --adaptive
+among them; spp/ and noise/ keep showing the measured counts and errors.  `sampling` gains `denoise`, the parameters.
 """
 import argparse
 import json
@@ -95,16 +103,18 @@ def load_fixed_bg(path, device, bg_res=512):
 
 
 @torch.no_grad()
-def render_frames(nerf, rays, focal, chunk, noise, sampling=None):
+def render_frames(nerf, rays, focal, chunk, noise, sampling=None, wh=None):
     """rays [F, h*w, 6] -> rgb [F, h*w, 3], seconds; render2completion over `chunk`-ray slices (renderer.py:56-106).  sampling =
-    dict(spp, min_spp, tol) with spp > 1: every frame is multisample.render_frame's mean over passes of the same rays"""
+    dict(spp, min_spp, tol[, denoise]) with spp > 1: every frame is multisample.render_frame's mean over passes of the same rays; a
+    denoised frame needs wh = [w, h], the shape its rays form"""
     out = []
+    frame = dict(frame_hw=(int(wh[1]), int(wh[0]))) if sampling and sampling.get("denoise") is not None else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for f in range(rays.shape[0]):
         if sampling and sampling["spp"] > 1:
             from .multisample import render_frame
-            out.append(render_frame(nerf, rays[f], focal, jitter=False, noise=noise, chunk=chunk, **sampling)[0]["rgb_map"])
+            out.append(render_frame(nerf, rays[f], focal, jitter=False, noise=noise, chunk=chunk, **sampling, **(frame or {}))[0]["rgb_map"])
         else:
             out.append(render_images(nerf, rays[f], focal, chunk, noise))
     torch.cuda.synchronize()
@@ -128,7 +138,7 @@ def light_turntable(nerf, rays, focal, chunk, noise, n, wh, out_dir=None, sampli
             turned.get_spherical_harmonics(100)                             # SH irradiance of the turned map
             torch.cuda.synchronize()
             env_s.append(round(time.perf_counter() - t0, 6))
-            rgb, dt = render_frames(nerf, rays, focal, chunk, noise, sampling)
+            rgb, dt = render_frames(nerf, rays, focal, chunk, noise, sampling, wh)
             render_s.append(round(dt, 6))
             if out_dir:
                 from PIL import Image
@@ -227,6 +237,10 @@ def main(argv=None):
                     help="with --spp: stop a pixel once the standard error of its displayed colour is below TOL / 255 "
                          f"(8-bit levels; without a value: {ADAPTIVE_DEFAULT:g})")
     ap.add_argument("--min-spp", type=int, default=None, metavar="N", help="with --adaptive: passes every pixel gets (default 4, at most --spp)")
+    ap.add_argument("--denoise", type=int, nargs="?", const=-100, default=None, metavar="LEVELS",
+                    help="with --spp 2 or more: filter every finished frame (variance-guided a-trous filter; LEVELS levels, default 3, 0 to 8)")
+    ap.add_argument("--denoise-strength", type=float, default=None, metavar="K_C",
+                    help="with --denoise: the width of the colour test in standard errors (default 4; larger smooths more)")
     edit.add_arguments(ap)
     args = ap.parse_args(argv)
     if args.spp < 1:
@@ -239,10 +253,27 @@ def main(argv=None):
         ap.error("--min-spp lies between 1 and --spp")
     if args.material_maps and args.spp > 1:
         ap.error("--material-maps with --spp above 1: the material maps are not accumulated")
+    denoise = None
+    if args.denoise_strength is not None and args.denoise is None:
+        ap.error("--denoise-strength needs --denoise")
+    if args.denoise is not None:
+        from .multisample import DenoiseParams
+        if args.spp < 2:
+            ap.error("--denoise needs --spp N with N > 1 (the filter is steered by the variance of a pixel's samples)")
+        if args.denoise != -100 and not 0 <= args.denoise <= 8:
+            ap.error("--denoise takes a number of levels from 0 to 8")
+        if args.denoise_strength is not None and not 0 < args.denoise_strength < float("inf"):
+            ap.error("--denoise-strength takes a finite width above 0 (in standard errors)")
+        given = dict(levels=args.denoise) if args.denoise != -100 else {}
+        if args.denoise_strength is not None:
+            given["k_c"] = args.denoise_strength
+        denoise = DenoiseParams(**given)
     sampling = None
     if args.spp > 1:
         sampling = dict(spp=args.spp, min_spp=args.min_spp if args.min_spp is not None else min(4, args.spp),
                         tol=None if args.adaptive is None else args.adaptive / 255.0)
+        if denoise is not None:
+            sampling["denoise"] = denoise
     composed = bool(args.insert) or args.place is not None
     placements = None
     if composed:
@@ -321,13 +352,15 @@ def main(argv=None):
     chunk = args.chunk or nerf.eval_batch_size
     noise = DeviceNoise(dev, seed=11)
     render_frames(nerf, rays[:1, : min(chunk, rays.shape[1])], focal, chunk, noise)          # warm-up (table builds)
-    rgb, dt = render_frames(nerf, rays, focal, chunk, noise, sampling)
+    rgb, dt = render_frames(nerf, rays, focal, chunk, noise, sampling, wh)
     rec = dict(frames=int(rays.shape[0]), width=wh[0], height=wh[1], chunk=chunk, seconds=round(dt, 4),
                rays_per_s=round(rays.shape[0] * rays.shape[1] / dt, 1), relit=bool(args.fixed_bg))
     if composed:
         rec.update(parts=len(placements), placements=[p.spec() for p in placements])
     if sampling:
         rec["sampling"] = dict(spp=sampling["spp"], min_spp=sampling["min_spp"], adaptive=args.adaptive)
+        if denoise is not None:
+            rec["sampling"]["denoise"] = denoise.record()
     if gt is not None:
         rec["psnr"] = round(float(torch.stack([psnr_8bit(rgb[i], gt[i]) for i in range(rgb.shape[0])]).mean()), 3)
     if args.out:

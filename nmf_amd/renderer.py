@@ -162,7 +162,7 @@ def write_material_maps(savePath, name, ims, H, W):
 
 @torch.no_grad()
 def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", N_samples=-1, white_bg=False, ndc_ray=False,
-             compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, spp=1, min_spp=4, tol=None, **kw):
+             compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, spp=1, min_spp=4, tol=None, denoise=None, **kw):
     """renderer.py:195-510 for the outputs the fused eval pass produces.  Per view of `iterator()` ((idx, im_idx, rays,
     gt_rgb [H,W,3] or None)): PSNR of the 8-bit prediction (psnr_8bit), with compute_extra_metrics its SSIM against the
     unclipped ground truth (renderer.py:403-404, nmf_ssim), and the normal error (renderer.py:357-390, nmf_normal_err) when
@@ -175,7 +175,8 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
     its astype(uint8) would wrap), spec/ and rgbd/ (depth) EXRs, renderer.py:433-463.
     spp > 1: every view is multisample.render_frame's mean of up to spp passes (min_spp, tol: its adaptive stop; the rays stay the data
     set's, through the pixel centres, which the scores are defined on) and spp/, noise/ PNGs are written (write_sample_maps); spp = 1 is
-    the single pass as before.  The material maps are not accumulated.
+    the single pass as before.  The material maps are not accumulated.  denoise: a multisample.DenoiseParams -- the view's rgb is the
+    filtered frame (the data set's image size is the frame's shape; needs spp >= 2); noise/ keeps the measured standard error.
     -> dict(psnrs, norm_errs, ssims, seconds=dict(render, metrics))."""
     from . import hip
     if ndc_ray:
@@ -187,6 +188,8 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
         raise ValueError(f"evaluate: spp is at least 1, got {spp}")
     if spp > 1 and material_maps:
         raise ValueError("evaluate: the material maps are not accumulated (material_maps needs spp = 1)")
+    if denoise is not None and spp < 2:
+        raise ValueError(f"evaluate: denoise needs spp >= 2, got spp = {spp}")
     if savePath is not None:
         for sub in ("", "world_normal", "acc_map", "err") + (MATERIAL_DIRS if material_maps else ()) + (SAMPLE_DIRS if spp > 1 else ()):
             os.makedirs(os.path.join(savePath, sub), exist_ok=True)
@@ -202,7 +205,8 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
         keys = ("rgb_map", "acc_map", "world_normal") + (("depth",) + MATERIAL_KEYS if material_maps else ())
         if spp > 1:
             from .multisample import render_frame
-            ims, _ = render_frame(tensorf, rays.to(device), focal, spp=spp, min_spp=min_spp, tol=tol, jitter=False, noise=noise, keys=keys)
+            ims, _ = render_frame(tensorf, rays.to(device), focal, spp=spp, min_spp=min_spp, tol=tol, jitter=False, noise=noise, keys=keys,
+                                  denoise=denoise, frame_hw=(H, W) if denoise is not None else None)
         else:
             ims = render_images(tensorf, rays.to(device), focal, noise=noise, keys=keys)
         rgb = ims["rgb_map"].reshape(H, W, 3)
@@ -262,9 +266,9 @@ def evaluate(iterator, test_dataset, tensorf, renderer, savePath=None, prtx="", 
 @torch.no_grad()
 def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=5, prtx="", N_samples=-1, white_bg=False,
                ndc_ray=False, compute_extra_metrics=True, device="cuda", noise=None, material_maps=False, spp=1, min_spp=4, tol=None,
-               **kw):
+               denoise=None, **kw):
     """renderer.py:513-560: every max(N // N_vis, 1)-th view of a stacked test set (all views with N_vis < 0) through
-    `evaluate`; the call shape of train.py:863-875.  spp, min_spp, tol: evaluate's multi-sample views."""
+    `evaluate`; the call shape of train.py:863-875.  spp, min_spp, tol, denoise: evaluate's multi-sample views."""
     n = test_dataset.all_rays.shape[0]
     step = 1 if N_vis < 0 else max(n // N_vis, 1)
     idxs = list(range(0, n, step))
@@ -277,7 +281,7 @@ def evaluation(test_dataset, tensorf, unused, renderer, savePath=None, *, N_vis=
 
     return evaluate(iterator, test_dataset, tensorf, renderer, savePath, prtx=prtx, N_samples=N_samples, white_bg=white_bg,
                     ndc_ray=ndc_ray, compute_extra_metrics=compute_extra_metrics, device=device, noise=noise,
-                    material_maps=material_maps, spp=spp, min_spp=min_spp, tol=tol, **kw)
+                    material_maps=material_maps, spp=spp, min_spp=min_spp, tol=tol, denoise=denoise, **kw)
 
 
 PATH_PANELS = dict(rgb="rgb_map", depth="depth", normal="world_normal", acc="acc_map")       # panel -> key of render_images, in strip order
@@ -298,7 +302,7 @@ def _write_animation(path, frames, animation, fps):
 
 @torch.no_grad()
 def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="", device="cuda", noise=None, panels=("rgb", "depth"),
-                    animation="apng", fps=30, camera=None, writer_depth=2, spp=1, min_spp=4, tol=None):
+                    animation="apng", fps=30, camera=None, writer_depth=2, spp=1, min_spp=4, tol=None, denoise=None):
     """renderer.py:564-582 (the call shape of train.py:884-901): renders the camera path c2ws [n, 4, 4] (camera-to-world, the loader's
     convention; nmf_amd/camera_path.py) into savePath.  `renderer` is ignored, as in `evaluation`.  The camera is test_dataset's
     (size, fx / fy, centred principal point, near_far) or camera = dict(w, h, fx, fy, cx, cy, near_far), with which test_dataset may
@@ -315,6 +319,8 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
     spp > 1: a frame is multisample.render_frame's mean of up to spp jittered passes from the pose (min_spp, tol: its adaptive stop;
     one FrameAccumulator for the path; the frame's device time is all under `render`), spp/ and noise/ PNGs are written on the calling
     thread (write_sample_maps) and the result gains rays_rendered and passes per frame.  spp = 1 runs the single pass as before.
+    denoise: a multisample.DenoiseParams -- every finished frame is filtered (needs spp >= 2; the filter's guides make every pass render
+    depth and normal whatever the panels are); spp/ and noise/ keep the measured counts and errors.
     -> dict(frames, panels, seconds=dict(rays, render, finish: device time from events; write_wait: the calling thread blocked on
     the writer; total: wall clock until the last frame is on disk; animation: the container), frame_ms=dict(rays, render, finish:
     the device times per frame), rays_per_s)."""
@@ -337,6 +343,8 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
     spp = int(spp)
     if spp < 1:
         raise ValueError(f"evaluation_path: spp is at least 1, got {spp}")
+    if denoise is not None and spp < 2:
+        raise ValueError(f"evaluation_path: denoise needs spp >= 2, got spp = {spp}")
     for sub in ("",) + tuple(PATH_DIRS[p] for p in panels if p in PATH_DIRS) + (SAMPLE_DIRS if spp > 1 else ()):
         os.makedirs(os.path.join(savePath, sub), exist_ok=True)
     keys = tuple(PATH_PANELS[p] for p in panels)
@@ -393,7 +401,7 @@ def evaluation_path(test_dataset, tensorf, c2ws, renderer, savePath, *, prtx="",
             if spp > 1:
                 ev[1].record()
                 ims, st = render_frame(tensorf, c2ws[k], cam, spp=spp, min_spp=min_spp, tol=tol, jitter=True, noise=noise, keys=keys,
-                                       accumulator=accumulator)
+                                       accumulator=accumulator, denoise=denoise)
                 sampled.append(st)
                 write_sample_maps(savePath, f"{prtx}{k:03d}", ims, H, W)
             else:
