@@ -54,7 +54,14 @@ __device__ __forceinline__ RayCtx load_ray(const nmf_march_params& p, const floa
     float az = fdiv(fsub(p.aabb_max[2], c.oz), vz), bz = fdiv(fsub(p.aabb_min[2], c.oz), vz);
     float t = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
     c.tmin = fminf(fmaxf(t, p.near_t), p.far_t);
-    c.tfar = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+    // tfar only ends the march early, so it must never come before the last step the in-box test (:195) accepts.  An axis the
+    // ray (almost) does not move along cannot end it: with |d| < 1e-3 the rounding of o + d z (~1e-6) is worth more than the
+    // 1e-2 margin in z, and a zero component (1e-6 above) whose origin lies ON a face gives an exit distance of 0 although
+    // every step stays on that face, which is inside.  Such axes are left out (the other axes, or n_steps, end the ray).
+    const float ex = fabsf(c.dx) < 1e-3f ? 3.0e38f : fmaxf(ax, bx);
+    const float ey = fabsf(c.dy) < 1e-3f ? 3.0e38f : fmaxf(ay, by);
+    const float ez = fabsf(c.dz) < 1e-3f ? 3.0e38f : fmaxf(az, bz);
+    c.tfar = fminf(fminf(ex, ey), ez);
     return c;
 }
 

@@ -67,9 +67,12 @@ namespace {
 constexpr int SEL_THREADS = 1024, SEL_PER = 2, SEL_CHUNK = SEL_THREADS * SEL_PER;
 constexpr int TOPK_SORT_IN_LDS = 4096;
 
-// fp32 -> uint32 whose unsigned order is the ascending float order (-0.0 < +0.0 like a stable radix sort of the bits; NaNs last)
+// fp32 -> uint32 whose unsigned order is the ascending float order.  -0.0 takes the code of +0.0: the two compare equal, and both
+// the library radix sort behind nmf_argsort_f32 and a stable comparison sort keep zeros of either sign in index order (the
+// select must cut and order ties exactly like them).  NaNs with a clear sign bit last.
 __device__ __forceinline__ uint32_t f2u(float f) {
-    const uint32_t b = __float_as_uint(f);
+    uint32_t b = __float_as_uint(f);
+    if (b == 0x80000000u) b = 0u;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 

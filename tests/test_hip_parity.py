@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import Golden, assert_close
+from march_cases import _philox4x32_10
 from oracle import nmf_oracle as O
 from test_composite_cpu import sequential_sum32
 
@@ -1571,20 +1572,6 @@ def test_multi_copy_pack_unpack():
     for t, o in zip(ts, out):
         assert o.stride() == t.stride() or t.numel() <= 1
         assert torch.equal(o.cpu().float(), t.float())
-
-
-def _philox4x32_10(ctr_lo, ctr_hi, seed):
-    """numpy Philox4x32-10 exactly as csrc/common.hpp: counter (lo64, hi64), key = seed (lo32, hi32) -> [n, 4] uint32"""
-    M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
-    c = [np.asarray(ctr_lo & 0xffffffff, np.uint64), np.asarray(ctr_lo >> 32, np.uint64),
-         np.full_like(np.asarray(ctr_lo, np.uint64), ctr_hi & 0xffffffff), np.full_like(np.asarray(ctr_lo, np.uint64), ctr_hi >> 32)]
-    a, b = np.uint64(seed & 0xffffffff), np.uint64(seed >> 32)
-    for _ in range(10):
-        p0, p1 = M0 * c[0], M1 * c[2]
-        hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & np.uint64(0xffffffff), p1 >> np.uint64(32), p1 & np.uint64(0xffffffff)
-        c = [hi1 ^ c[1] ^ a, lo1, hi0 ^ c[3] ^ b, lo0]
-        a, b = (a + np.uint64(0x9E3779B9)) & np.uint64(0xffffffff), (b + np.uint64(0xBB67AE85)) & np.uint64(0xffffffff)
-    return np.stack(c, -1).astype(np.uint32)
 
 
 def test_march_in_kernel_philox_equals_explicit_jitter():
